@@ -2,15 +2,26 @@
 """Headline benchmark: SAR tiles/sec of one SNUNet-ECAM change-detection TRAIN STEP
 (forward + CE+Dice loss + backward + Adam [+ gradient all-reduce]) on 224x224 tiles.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Workload (BASELINE.json configs[1]): SNUNet-ECAM, 2 dates x 2-ch GRD (VV,VH) 224x224, per-GPU
 batch 32, bf16 activations / fp32 parameters+accumulation, synthetic tiles, random-init weights.
 Weak scaling: every rank processes its own 32 tiles per step; value = total tiles / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus `roofline` (dominant kernel class,
-HIP-event timed inside the timed region) and `cpu_baseline` (CPU oracle port on host cores).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): metric, value,
+unit, higher_is_better, dtype, ms_per_step (= wall clock of the K timed steps / K) and the per-step
+event figures of the timed region.  --full adds everything else: the kernel-class calibration step,
+`roofline` (dominant kernel family, HIP-event timed in extra steps after the timed region, measured
+HBM / GEMM peaks of the part), `cpu_baseline` (CPU oracle port on host cores), `kernels`
+(--time-all), `config.dp_check` (data parallel) and the BENCH_LAUNCH_MAP / BENCH_DETAIL tables.
+
+--dump-outputs DIR writes what the last timed step computed (DIR/<name>.npy, float32): `loss`
+(the step's loss vector), the model output -- `logits` (the output map of every model but MAE) or
+`pred` (MAE: the pixel values predicted for the masked patches) -- and `params` (the updated
+parameters); an array of more than DUMP_MAX_ELEMS elements is written as DUMP_MAX_ELEMS of its
+elements, drawn without replacement at fixed, seeded positions and kept in index order.  Inputs and initial
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +45,36 @@ MFMA_BF16_PEAK_TF = 2500.0   # dense bf16
 
 IN_STEP_STEPS = 4    # multi-stream steps AFTER the timed region whose dominant-class launches carry HIP event pairs (roofline.in_step);
                      # the timed region itself carries one event per step boundary only (ms_per_step_p50)
+DUMP_MAX_ELEMS = 1 << 22     # --dump-outputs: larger arrays are written as a seeded sample of exactly this many elements (16 MiB of float32)
+
+
+def snapshot_outputs(step):
+    """host copies (float32) of what a caller of the train step receives: the loss vector, the model output (`logits`; MAE: `pred`,
+    the pixel values predicted for the masked patches) and the updated parameters.  Arrays above DUMP_MAX_ELEMS elements are sampled
+    without replacement at fixed, seeded positions (the same for every run with the same arguments), in index order."""
+    import numpy as np
+    arrays = {"loss": step.loss_out, "params": step.model.flat_params}
+    if getattr(step.plan, "logits", None) is not None:
+        arrays["logits"] = step.plan.logits
+    elif "pred" in getattr(step.plan, "named", {}):
+        arrays["pred"] = step.plan.named["pred"]
+    else:
+        raise RuntimeError(f"--dump-outputs: {type(step.plan).__name__} exposes no model output")
+    out = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240611).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        out[name] = flat.float().cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 class KernelTimer:
@@ -433,15 +474,24 @@ def main():
     ap.add_argument("--channels", type=int, default=2, help="bands per date: 2 = GRD (VV, VH), 4 = SLC (BASELINE.json configs[3] as written)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--net-g", default="base_resnet18", help="--model bit-cd: net_G of define_G (models/bit_cd.py:686-707)")
-    ap.add_argument("--time-all", action="store_true", help="HIP-event time every kernel class (diagnostic)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline: kernel-class calibration, roofline (extra timed steps, HBM / GEMM peak "
+                         "probes), CPU baseline, data-parallel check; the options below marked --full only act with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, model output (logits; MAE: pred) and parameters of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--time-all", action="store_true", help="(--full) HIP-event time every kernel class (diagnostic)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
     ap.add_argument("--no-solo", action="store_true",
-                    help="skip the single-stream steps after the timed region (roofline.solo); the rocprof passes use it so that a trace "
-                         "holds the launches of ONE mode")
+                    help="(--full) skip the single-stream steps after the timed region (roofline.solo); the rocprof passes use it so that "
+                         "a trace holds the launches of ONE mode")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as ONE captured HIP graph in the timed region (single GPU); the per-kernel roofline figures "
                          "then come from eager steps run after it")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.time_all and not args.full:
+        ap.error("--time-all is a --full diagnostic")
 
     # The contract is ONE JSON line on stdout.  Libraries write banners to the C-level stdout (RCCL prints its version block when a
     # communicator is created / destroyed): send file descriptor 1 to stderr for the life of the process and keep a private copy
@@ -558,27 +608,33 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- warm-up (one of the warm-up steps also picks the dominant kernel class with every launch timed; not the very first
-    # step when there are two or more: first launches carry one-off code-object loads) -------------
-    if args.warmup >= 2:
+    # ---- warm-up: max(W, 1) steps.  --full: one of them also picks the dominant kernel class with every launch timed (not the very
+    # first step when there are two or more: first launches carry one-off code-object loads); a plain run takes the same number of
+    # steps, so both start the timed region from the same state -------------
+    if args.full:
+        if args.warmup >= 2:
+            step.run()
+        calib = KernelTimer(None)
+        step.timer = calib
         step.run()
-    calib = KernelTimer(None)
-    step.timer = calib
-    step.run()
-    torch.cuda.synchronize()
-    cs = calib.summary()
-    dominant = max((k for k in cs if k.startswith("igemm") or k.startswith("gemm")), key=lambda k: cs[k]["ms"])
-    step.timer = None
-    for _ in range(max(args.warmup - 2, 0)):
-        step.run()
+        torch.cuda.synchronize()
+        cs = calib.summary()
+        dominant = max((k for k in cs if k.startswith("igemm") or k.startswith("gemm")), key=lambda k: cs[k]["ms"])
+        step.timer = None
+        for _ in range(max(args.warmup - 2, 0)):
+            step.run()
+    else:
+        for _ in range(max(args.warmup, 1)):
+            step.run()
     # ---- timed region ----------------------------------------------------------------------------
-    timer = KernelTimer(None if args.time_all else {dominant})
+    timer = KernelTimer(None if args.time_all else {dominant}) if args.full else None
     graph = args.graph and world == 1 and hasattr(step, "capture_graph")
     if graph:
         step.capture_graph()
     else:
         step.timer = timer
-    timer.active = bool(args.time_all)          # (--time-all is a diagnostic: its value is not the benchmark's)
+    if timer is not None:
+        timer.active = bool(args.time_all)      # (--time-all is a diagnostic: its value is not the benchmark's)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     sync()
     t0 = time.perf_counter()
@@ -596,39 +652,43 @@ def main():
     dt = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     p50_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-    # roofline.in_step: the dominant kernel class inside the multi-stream step, bracketed in a few steps BEHIND the timed region
-    timer.active = True
-    timer_steps = args.steps if args.time_all else min(args.steps, IN_STEP_STEPS)
-    if graph:           # HIP events cannot bracket the nodes of a replayed graph: eager steps
-        step._graph = None
-    if not args.time_all:
-        step.timer = timer
-        for _ in range(timer_steps):
-            step.run()
-        sync()
-    # ---- the kernels alone on the machine ("solo"): with more than one stream (trainer.py overlap_wgrad / overlap_lanes) the launches
-    # timed above shared the GPU with the other streams, so their durations describe the overlapped step, not the kernel.  A few more
-    # steps on ONE stream with EVERY launch bracketed by HIP events (on the stream it is launched on) give per-kernel durations that
-    # a rocprofv3 --kernel-trace of a single-stream run reproduces; the library reports which kernel instantiation each launch
-    # started (ksmi_last_kernels), so every record carries the name it has in the rocprofv3 tables under profiles/.
+    # what the last timed step computed, taken before any --full step below moves the state on
+    outputs = snapshot_outputs(step) if args.dump_outputs and rank == 0 else None
     n_streams = (1 + int(bool(getattr(step, "overlap_wgrad", False) and getattr(step.plan, "side_wgrad", False)))
                  + int(bool(getattr(step, "overlap_lanes", False) and getattr(step.plan, "two_lanes", False))))
     two_streams = n_streams > 1
-    solo_timer, solo_steps = None, 0
-    if not args.no_solo and hasattr(step, "overlap_wgrad"):
-        solo_timer = KernelTimer(None, names=True)
-        keep = (step.overlap_wgrad, step.overlap_lanes, getattr(step, "_graph", None))
-        step.timer, step.overlap_wgrad, step.overlap_lanes, step._graph = solo_timer, False, False, None
-        solo_steps = min(args.steps, 3)
-        for _ in range(solo_steps):
-            step.run()
-        sync()
-        step.timer, step.overlap_wgrad, step.overlap_lanes, step._graph = (timer if not graph else None), keep[0], keep[1], keep[2]
+    timer_steps, solo_timer, solo_steps = 0, None, 0
+    if args.full:
+        # roofline.in_step: the dominant kernel class inside the multi-stream step, bracketed in a few steps BEHIND the timed region
+        timer.active = True
+        timer_steps = args.steps if args.time_all else min(args.steps, IN_STEP_STEPS)
+        if graph:           # HIP events cannot bracket the nodes of a replayed graph: eager steps
+            step._graph = None
+        if not args.time_all:
+            step.timer = timer
+            for _ in range(timer_steps):
+                step.run()
+            sync()
+        # ---- the kernels alone on the machine ("solo"): with more than one stream (trainer.py overlap_wgrad / overlap_lanes) the
+        # launches timed above shared the GPU with the other streams, so their durations describe the overlapped step, not the kernel.
+        # A few more steps on ONE stream with EVERY launch bracketed by HIP events (on the stream it is launched on) give per-kernel
+        # durations that a rocprofv3 --kernel-trace of a single-stream run reproduces; the library reports which kernel instantiation
+        # each launch started (ksmi_last_kernels), so every record carries the name it has in the rocprofv3 tables under profiles/.
+        if not args.no_solo and hasattr(step, "overlap_wgrad"):
+            solo_timer = KernelTimer(None, names=True)
+            keep = (step.overlap_wgrad, step.overlap_lanes, getattr(step, "_graph", None))
+            step.timer, step.overlap_wgrad, step.overlap_lanes, step._graph = solo_timer, False, False, None
+            solo_steps = min(args.steps, 3)
+            for _ in range(solo_steps):
+                step.run()
+            sync()
+            step.timer, step.overlap_wgrad, step.overlap_lanes, step._graph = (timer if not graph else None), keep[0], keep[1], keep[2]
     dp_check = None
     if world > 1:
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
+    if world > 1 and args.full:
         # data-parallel self-check: every rank started from the same parameters and applied the same averaged gradients, so the
         # parameter arenas must agree bit for bit (an integer checksum of the fp32 words) although every rank saw different tiles
         fp = step.model.flat_params
@@ -643,13 +703,7 @@ def main():
     loss = step.loss_out.cpu().tolist()
 
     if rank == 0:
-        ts = timer.summary()
-        d = ts[dominant]
-        step_flops = sum(c[3]["flops"] for c in step.plan.fwd.calls + step.plan.bwd.calls)
-        step_bytes = sum(c[3]["bytes"] for c in step.plan.fwd.calls + step.plan.bwd.calls)
         ms_step = dt / args.steps * 1e3
-        peaks = measure_hbm_peaks(dev) if world == 1 and not args.no_solo else None      # (--no-solo: the rocprofv3 passes trace the step only)
-        hbm_meas = max(peaks["copy_GBs"], peaks["triad_GBs"], peaks["copy_torch_GBs"], peaks["triad_torch_GBs"]) if peaks else HBM_MEASURED_GBS
         res = {
             "metric": metric,
             "value": round(B * world * args.steps / dt, 2), "unit": "tiles/s",
@@ -667,6 +721,13 @@ def main():
                                      "ms_per_step = wall clock / steps (the value), ms_per_step_p50 = median of per-step HIP-event intervals",
                        "loss_last": [round(x, 5) for x in loss]} | ({"dp_check": dp_check} if dp_check else {}),
         }
+    if rank == 0 and args.full:
+        ts = timer.summary()
+        d = ts[dominant]
+        step_flops = sum(c[3]["flops"] for c in step.plan.fwd.calls + step.plan.bwd.calls)
+        step_bytes = sum(c[3]["bytes"] for c in step.plan.fwd.calls + step.plan.bwd.calls)
+        peaks = measure_hbm_peaks(dev) if world == 1 and not args.no_solo else None      # (--no-solo: the rocprofv3 passes trace the step only)
+        hbm_meas = max(peaks["copy_GBs"], peaks["triad_GBs"], peaks["copy_torch_GBs"], peaks["triad_torch_GBs"]) if peaks else HBM_MEASURED_GBS
         res["roofline"] = build_roofline(args, step, solo_timer, solo_steps, d, dominant, timer_steps, ms_step, step_bytes, step_flops,
                                          peaks, hbm_meas, two_streams)
         if args.time_all:
@@ -687,9 +748,9 @@ def main():
                       f"{meta['flops'] * n / ms / 1e9:7.1f} TF/s {meta['bytes'] * n / ms / 1e6:7.1f} GB/s", file=sys.stderr)
         if world == 1 and not args.no_cpu_baseline and args.model == "snunet":
             res["cpu_baseline"] = cpu_baseline()
-        result_line = json.dumps(res)
-    else:
-        result_line = None
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
+    result_line = json.dumps(res) if rank == 0 else None
     if dist.is_initialized():
         dist.destroy_process_group()
     if result_line is not None:

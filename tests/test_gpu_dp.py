@@ -292,7 +292,7 @@ def _torchrun_bench(nproc, extra_env=None, args=()):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **(extra_env or {}))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "5", "--warmup", "2",
-           "--no-cpu-baseline", "--no-solo", *args]
+           "--full", "--no-cpu-baseline", "--no-solo", *args]             # (--full: config.dp_check)
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -43,15 +43,15 @@ def test_json5_loader_handles_comments_and_trailing_commas(tmp_path):
     assert load_json5(p) == {"a": 1, "url": "http://x//y", "l": [1, 2]}
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/configs"), reason="reference not mounted")
-def test_json5_loader_reads_reference_config_files():
-    c = load_json5("/root/reference/configs/config.json")
+def test_json5_loader_reads_reference_config_files(golden_dir):
+    ref = os.path.join(golden_dir, "reference_configs")         # the reference's own config files, stored verbatim
+    c = load_json5(os.path.join(ref, "config.json"))
     assert c["num_classes"] == 3 and c["task"] == "segmentation"
-    d = load_json5("/root/reference/configs/train/data_config.json")
+    d = load_json5(os.path.join(ref, "train/data_config.json"))
     mine = load_json5(os.path.join(ROOT, "configs/train/data_config.json"))
     for k in ("data_mean", "data_std", "dem_mean", "dem_std", "clamp_input", "inputs", "channels", "train_acts", "val_acts", "test_acts"):
         assert d[k] == mine[k], k
-    s = load_json5("/root/reference/configs/method/snunet/snunet.json")
+    s = load_json5(os.path.join(ref, "method/snunet/snunet.json"))
     m = load_json5(os.path.join(ROOT, "configs/method/snunet/snunet.json"))
     assert s == {k: m[k] for k in s}
 

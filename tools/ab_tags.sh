@@ -1,11 +1,14 @@
 #!/bin/bash
 # same-box solo times (us) per (kind, tag) under environment settings, for kinds matching a prefix: bash tools/ab_tags.sh "<kind prefix>" "<VAR=val>" ...
 pre="$1"; shift
+export OUT=${OUT:-bench_out}    # output folder
+mkdir -p $OUT
 for cfg in "$@"; do
-  env $cfg BENCH_LAUNCH_MAP=/tmp/map.json python bench.py --steps 10 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
+  rm -f $OUT/map.json    # (a failed run must not leave the previous configuration's table to be read)
+  env $cfg BENCH_LAUNCH_MAP=$OUT/map.json python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > /dev/null 2>&1
   python - "$pre" "$cfg" <<'PY'
-import json, sys, collections
-m = json.load(open("/tmp/map.json"))
+import os, json, sys, collections
+m = json.load(open(os.environ["OUT"] + "/map.json"))
 agg = collections.OrderedDict()
 for e in m:
     if e["kind"].startswith(sys.argv[1]):

@@ -1,12 +1,13 @@
 #!/bin/bash
-# solo times of the 3x3 weight-gradient launches under forced workgroup counts (GPU box) -> gpurun_out/w3wgs.txt
-mkdir -p gpurun_out
+# solo times of the 3x3 weight-gradient launches under forced workgroup counts (GPU box) -> $OUT/w3wgs.txt
+export OUT=${OUT:-bench_out}    # output folder
+mkdir -p $OUT
 {
 for n in 0 256 384 512 768 1024; do
-KSMI_WGRAD3_WGS=$n BENCH_LAUNCH_MAP=gpurun_out/map_w3wgs_$n.json python bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+KSMI_WGRAD3_WGS=$n BENCH_LAUNCH_MAP=$OUT/map_w3wgs_$n.json python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 python - $n <<'PY'
-import json, sys
-m = json.load(open(f"gpurun_out/map_w3wgs_{sys.argv[1]}.json"))
+import os, json, sys
+m = json.load(open(f"{os.environ['OUT']}/map_w3wgs_{sys.argv[1]}.json"))
 r = [e for e in m if e["kind"] == "igemm_wgrad<3x3s1>"]
 print(f"WGS={sys.argv[1]}: total {sum(e['ms'] for e in r)*1e3:.1f} us")
 seen = {}
@@ -16,5 +17,5 @@ for e in r:
 for k, v in seen.items(): print(f"   {k:32s} {sum(v)/len(v):7.1f} us x{len(v)}")
 PY
 done
-} > gpurun_out/w3wgs.txt 2>&1
-cat gpurun_out/w3wgs.txt
+} > $OUT/w3wgs.txt 2>&1
+cat $OUT/w3wgs.txt

@@ -1,4 +1,4 @@
-"""top launches of the last single-stream step per model (BENCH_LAUNCH_MAP json written by bench.py): python tools/launch_map_top.py m1 m2 ..."""
+"""top launches of the last single-stream step per model (BENCH_LAUNCH_MAP json written by bench.py --full): python tools/launch_map_top.py m1 m2 ..."""
 import json, sys
 for m in sys.argv[1:]:
     rows = json.load(open(f"gpurun_out/lm_{m}.json"))
