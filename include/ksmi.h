@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define KSMI_ABI_VERSION 7   /* 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list, fused SR-attention block, stream-K token GEMMs); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
+#define KSMI_ABI_VERSION 7   /* 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list; later, backward-compatible: the dice / Lovasz / focal losses ksmi_seg_loss_workspace, _forward, _backward); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
 #define KSMI_F32 0
 #define KSMI_BF16 1
 #define KSMI_E_ARG (-1)
@@ -398,6 +398,30 @@ int ksmi_ce_dice_forward(const float* logits, const int64_t* labels, const float
 int ksmi_ce_dice_backward(const float* logits, const int64_t* labels, const float* class_w, int with_dice,
                           const float* workspace, const float* grad_scale /* device scalar or NULL (=1) */,
                           float* dlogits, int B, int HW, int ignore_index, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The other losses of create_loss (utilities/utilities.py:323-341), csrc/loss.hip.  logits NCHW fp32 [B,3,H,W] (or log-probabilities:
+ * same softmax), labels int64 [B,H,W]; pixels whose label == ignore_index contribute nothing and get a zero gradient.
+ *   KSMI_LOSS_DICE   smp DiceLoss(mode="multiclass", ignore_index): p = softmax; per class, sums over the WHOLE batch
+ *                    I = sum p t, D = sum (v p + t); loss = mean over the 3 classes of (1 - 2 I / max(D, 1e-7)) [sum t > 0]
+ *   KSMI_LOSS_LOVASZ smp LovaszLoss(mode="multiclass", per_image=False): Lovasz-softmax over the flattened batch, mean over the
+ *                    classes present; errors sorted descending by a STABLE sort (ties keep the (b, h, w) order)
+ *   KSMI_LOSS_FOCAL  FocalLoss(alpha = class_w, gamma, reduction="mean"): sum alpha[y] (1 - pt)^gamma (-log pt) / #valid pixels;
+ *                    gamma must be 0 or >= 1
+ * class_w (3 floats) and gamma are read by the focal loss only (NULL / any value otherwise).  out3 = {loss, 0, 0}.  The workspace
+ * (bytes from the _workspace query: O(B HW) for Lovasz, O(B) otherwise) carries the backward coefficients from the forward to the
+ * backward; nothing is allocated or read back inside either call.  Bit-reproducible: fixed-order reductions, no float atomics.
+ * ------------------------------------------------------------------------------- */
+#define KSMI_LOSS_DICE 1
+#define KSMI_LOSS_LOVASZ 2
+#define KSMI_LOSS_FOCAL 3
+size_t ksmi_seg_loss_workspace(int kind, int B, int HW);
+int ksmi_seg_loss_forward(int kind, const float* logits, const int64_t* labels, const float* class_w, float gamma, float* out3,
+                          void* workspace, int B, int HW, int ignore_index, void* stream);
+/* dlogits = grad_scale * d loss / d logits ; must follow the forward of the same kind on the same workspace */
+int ksmi_seg_loss_backward(int kind, const float* logits, const int64_t* labels, const float* class_w, float gamma,
+                           const void* workspace, const float* grad_scale /* device scalar or NULL (=1) */,
+                           float* dlogits, int B, int HW, int ignore_index, void* stream);
 
 /* Metrics: predictions = argmax(1) (lowest index on ties), cm[4][4] int64 += counts of
  * (target,pred) over target != ignore_index.  training/change_detection_trainer.py:152,184-189;

@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libksmi.so")
 
 KSMI_F32, KSMI_BF16 = 0, 1
+LOSS_DICE, LOSS_LOVASZ, LOSS_FOCAL = 1, 2, 3          # KSMI_LOSS_* (ksmi_seg_loss_*)
 MAX_SRC, MAX_CHUNKS = 6, 72
 ABI_VERSION = 7
 
@@ -162,6 +163,9 @@ SIGNATURES = {
     "ksmi_loss_workspace": (_sz, [_i, _i]),
     "ksmi_ce_dice_forward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "ksmi_ce_dice_backward": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "ksmi_seg_loss_workspace": (_sz, [_i, _i, _i]),
+    "ksmi_seg_loss_forward": (_i, [_i, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _vp]),
+    "ksmi_seg_loss_backward": (_i, [_i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ksmi_argmax_confusion": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ksmi_argmax_confusion_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ksmi_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _f, _vp]),

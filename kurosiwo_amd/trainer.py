@@ -14,6 +14,11 @@ from .optim import FusedAdam
 from .runtime import stream_ptr
 
 
+# create_loss's other criteria (loss.py) -> ksmi_seg_loss_* kind; focal with the class weights and gamma = 2 as create_loss builds it
+_SEG_LOSS_KINDS = {"dice": _lib.LOSS_DICE, "iou": _lib.LOSS_LOVASZ, "focal": _lib.LOSS_FOCAL}
+_FOCAL_GAMMA = 2.0
+
+
 def _optimizer_step(step, mf, plan):
     """optimizer.step on the flat arenas; an Adam-family optimiser also refreshes the plan's bf16 operand copy of the parameters (the
     next forward then skips its cast pass: plan_base.mirror_written)"""
@@ -31,7 +36,7 @@ class _PlanTrainStep:
 
     def __init__(self, model, plan, B, H, W, loss_function="ce+dice", class_weights=(1.0, 1.0, 1.0), optimizer=None, lr=1e-3,
                  bucket_mb=8.0, group=None, graph=False, overlap_wgrad=True, overlap_lanes=True, grad_dtype=None, dp_mode=None):
-        if loss_function not in ("ce+dice", "cross_entropy"):
+        if loss_function not in ("ce+dice", "cross_entropy") and loss_function not in _SEG_LOSS_KINDS:
             raise NotImplementedError(loss_function)
         self.model = model
         self.lib = _lib.load()
@@ -39,9 +44,11 @@ class _PlanTrainStep:
         dev = self.plan.dev
         self.B, self.HW = B, H * W
         self.with_dice = 1 if loss_function == "ce+dice" else 0
+        self.seg_kind = _SEG_LOSS_KINDS.get(loss_function)      # None: the ce / ce+dice kernels of head.hip
         self.cw = torch.tensor(list(class_weights), dtype=torch.float32, device=dev)
         self.loss_out = torch.zeros(3, dtype=torch.float32, device=dev)
-        self.loss_ws = torch.empty(self.lib.ksmi_loss_workspace(B, self.HW), dtype=torch.uint8, device=dev)
+        ws = self.lib.ksmi_loss_workspace(B, self.HW) if self.seg_kind is None else self.lib.ksmi_seg_loss_workspace(self.seg_kind, B, self.HW)
+        self.loss_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
         self.optimizer = optimizer if optimizer is not None else FusedAdam(model.parameters(), lr=lr)
         n = model.flat_params.numel()
@@ -153,12 +160,21 @@ class _PlanTrainStep:
         p.packs.run(t)
         p.fwd.run(t, None, self._streams())
         B, HW = self.B, self.HW
-        self._timed("ce_dice_forward", lambda: _lib.check(lib.ksmi_ce_dice_forward(
-            p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), self.with_dice, self.loss_out.data_ptr(),
-            self.loss_ws.data_ptr(), B, HW, 3, st), "ce_dice_forward"))
-        self._timed("ce_dice_backward", lambda: _lib.check(lib.ksmi_ce_dice_backward(
-            p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), self.with_dice, self.loss_ws.data_ptr(), None,
-            p.dlogits.data_ptr(), B, HW, 3, st), "ce_dice_backward"))
+        if self.seg_kind is None:
+            self._timed("ce_dice_forward", lambda: _lib.check(lib.ksmi_ce_dice_forward(
+                p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), self.with_dice, self.loss_out.data_ptr(),
+                self.loss_ws.data_ptr(), B, HW, 3, st), "ce_dice_forward"))
+            self._timed("ce_dice_backward", lambda: _lib.check(lib.ksmi_ce_dice_backward(
+                p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), self.with_dice, self.loss_ws.data_ptr(), None,
+                p.dlogits.data_ptr(), B, HW, 3, st), "ce_dice_backward"))
+        else:                                        # dice / iou / focal (csrc/loss.hip); loss_out = [loss, 0, 0]
+            k = self.seg_kind
+            self._timed("seg_loss_forward", lambda: _lib.check(lib.ksmi_seg_loss_forward(
+                k, p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), _FOCAL_GAMMA, self.loss_out.data_ptr(),
+                self.loss_ws.data_ptr(), B, HW, 3, st), "seg_loss_forward"))
+            self._timed("seg_loss_backward", lambda: _lib.check(lib.ksmi_seg_loss_backward(
+                k, p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), _FOCAL_GAMMA, self.loss_ws.data_ptr(), None,
+                p.dlogits.data_ptr(), B, HW, 3, st), "seg_loss_backward"))
         ss = self._streams()
         p.bwd.run(t, self._after_launch if ss is not None else self.reducer.after_launch, ss, hook_at=self.reducer.hook_indices())
         if ss is not None:
