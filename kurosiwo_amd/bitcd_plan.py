@@ -14,7 +14,7 @@ import torch
 from .bitcd import LAYERS
 from .changeformer_plan import CS
 from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
-from .snunet_plan import _Saved
+from .plan_base import _Saved
 from .unet_plan import UnetPlan
 
 

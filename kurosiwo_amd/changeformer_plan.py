@@ -13,9 +13,8 @@ import torch
 
 from . import _lib
 from .changeformer import DEPTHS, EMBED_DIMS, NUM_HEADS, SR_RATIOS
-from .plan_base import PlanBase
+from .plan_base import PlanBase, _Saved
 from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
-from .snunet_plan import _Saved
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 CS = 8            # channel stride of the 3-channel NHWC heads (vector-aligned pad channels)

@@ -5,10 +5,10 @@
 // launches of an SNUNet step, 29 ms for ChangeFormer's ~730 (bench `host_issue_ms_per_step`), i.e. the step was about to become
 // host-bound.  Here the list is compiled ONCE into an array of ksmi_op (function pointer, thunk of its
 // signature, 64-bit argument slots, lane / side-stream tags) and ksmi_run_list replays a segment of it: the same launches on the same
-// streams with the same event record / wait pairs as snunet_plan.LaunchList.run (the Python walk stays as the timed / hooked path and
+// streams with the same event record / wait pairs as launch.LaunchList.run (the Python walk stays as the timed / hooked path and
 // as the cross-check: tests/test_gpu_graph.py holds the two to the same bits).
 //
-// Streams (snunet_plan.StepStreams): main = lane 0, lane1 = second compute lane, side / side2 = weight-gradient streams.
+// Streams (launch.StepStreams): main = lane 0, lane1 = second compute lane, side / side2 = weight-gradient streams.
 //   CALL, plain:     launch on the stream of its lane.
 //   CALL, side:      the side stream waits for an event recorded on the launch's lane stream ("fork"), the launch goes to the side
 //                    stream, and a tagged launch records an event there that a later WAIT_SIDE(tag) consumes.

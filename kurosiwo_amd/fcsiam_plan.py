@@ -19,7 +19,7 @@ import torch
 from .changeformer_plan import CS, drop_threshold
 from .fcsiam import DECODER, ENCODER
 from .runtime import SrcSpec, make_conv, make_wgrad
-from .snunet_plan import _Saved
+from .plan_base import _Saved
 from .unet_plan import UnetPlan
 
 LAYERS = [n for st in ENCODER for n, _ in st] + [n for _, _, ch in DECODER for n, _ in ch]     # Dropout2d site = 2 * index + date

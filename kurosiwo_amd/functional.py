@@ -1,5 +1,5 @@
 """Functional (allocate-and-run) wrappers over the C-ABI conv family; used by the tests and
-by one-off callers.  The model plans (snunet_plan.py) build the same descriptors once and
+by one-off callers.  The model plans (plan_base.py and the *_plan.py modules) build the same descriptors once and
 replay them instead."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-"""Shared machinery of the static launch plans (FloodViT, ChangeFormer): scratch bookkeeping, weight packing, the
+"""Shared machinery of the static launch plans (every model family): scratch bookkeeping, weight packing, the
 launch-list wrappers around ksmi_conv_forward / ksmi_conv_wgrad for nn.Linear, nn.LayerNorm and ConvTranspose2d(k4,s2,p1)."""
 import ctypes as C
 import os
@@ -7,13 +7,22 @@ import torch
 
 from . import _lib
 from .runtime import DT, SrcSpec, conv_npad, make_conv, make_pack, make_wgrad, packed_weight_numel
-from .snunet_plan import LaunchList
+from .launch import LaunchList
 
 LN_EPS = 1e-5
 
 
+class _Saved:
+    """saved statistics of one BatchNorm call: rows = mean, rstd, scale, shift"""
+
+    def __init__(self, Cch, device):
+        self.t = torch.zeros((4, Cch), dtype=torch.float32, device=device)
+        self.mean, self.rstd, self.scale, self.shift = (self.t[i].data_ptr() for i in range(4))
+        self.scale_t, self.shift_t = self.t[2], self.t[3]
+
+
 class PlanBase:
-    # Weight-gradient launches may run on the train step's side stream (trainer.py overlap_wgrad, snunet_plan.StepStreams) only in plans where (a) every user of
+    # Weight-gradient launches may run on the train step's side stream (trainer.py overlap_wgrad, launch.StepStreams) only in plans where (a) every user of
     # the "wgrad" scratch goes through _wgrad (true here: the lane keeps them in order) and (b) no operand of a weight gradient is
     # rewritten by a later launch of the same backward pass.  (b) holds for the convolutional plans, whose activations and gradients
     # are dedicated buffers; the token plans (ChangeFormer encoder, FloodViT, MAE) recycle their per-block gradient buffers.
@@ -23,7 +32,10 @@ class PlanBase:
     side_tokens = False
     slab_bias_side = False     # bias rows of split-mode token weight gradients also from side-stream launches (_linear_wgrad)
 
-    def _init_base(self, model, dtype, with_backward):
+    pack_kind = "pack_weights"     # meta["kind"] of the batched weight-pack launch (bench.py groups by it)
+
+    def _init_lists(self, model, dtype, with_backward):
+        """what every plan has: the three launch lists and the bookkeeping behind them"""
         self.m, self.dtype, self.with_backward = model, dtype, with_backward
         self.dev = model.flat_params.device
         self.dt = DT[dtype]
@@ -39,8 +51,11 @@ class PlanBase:
         # (read per plan, not at import: tests and A/B runs vary them between plans of one process)
         self.csum_rows = max(1, int(os.environ.get("KSMI_CSUM_ROWS", "512")))
         self.rowsum_batch = max(1, int(os.environ.get("KSMI_ROWSUM_BATCH", "16")))
-        # bf16 mirror of the parameter arena for the token GEMMs (gemm.hip): one cast launch per step
         self.wb = None
+
+    def _init_base(self, model, dtype, with_backward):
+        """_init_lists + the bf16 mirror of the parameter arena for the token GEMMs (gemm.hip): one cast launch per step"""
+        self._init_lists(model, dtype, with_backward)
         if dtype == torch.bfloat16 and not os.environ.get("KSMI_LINEAR_IGEMM"):
             n = model.flat_params.numel()
             assert n % 8 == 0
@@ -81,8 +96,12 @@ class PlanBase:
 
     csum_rows, rowsum_batch = 512, 16          # class defaults; _init_base reads KSMI_CSUM_ROWS / KSMI_ROWSUM_BATCH per plan
 
+    def _before_pack_table(self):
+        """launches a plan appends once its graph is built, ahead of the batched weight pack (SNUNetPlan)"""
+
     def _finish(self):
         self._flush_rowsums()
+        self._before_pack_table()
         if self._pack_descs:
             n = len(self._pack_descs)
             arr = (_lib.PackDesc * n)(*self._pack_descs)
@@ -90,7 +109,7 @@ class PlanBase:
             table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
             self.keep.append(table)
             self.packs.add("ksmi_pack_weights_batched", lambda: (table.data_ptr(), n, self.dt),
-                           {"kind": "pack_weights", "bytes": 0, "flops": 0})
+                           {"kind": self.pack_kind, "bytes": 0, "flops": 0})
         for name, nbytes in self._need.items():
             self._bufs[name] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.dev)
         for fn in self._later:
@@ -130,6 +149,7 @@ class PlanBase:
         return acc
 
     def _mark(self, *keys):
+        """the launch just appended to self.bwd is (so far) the last writer of these gradients"""
         for k in keys:
             self.param_ready[k] = len(self.bwd.pending) - 1
 
@@ -193,8 +213,8 @@ class PlanBase:
         self._pack_descs.append(d)
         return out
 
-    def _conv(self, ll, d, tag, name=""):
-        self.keep.append(d)
+    def _conv_meta(self, d, tag, variant=""):
+        """roofline bookkeeping of one ksmi_conv_forward launch over descriptor d -> (meta, K, output pixels)"""
         d.dir = 1 if "dgrad" in tag else 0            # (profiling tag: kernel names carry the direction, ksmi.h)
         taps, es = d.KH * d.KW, self._es()
         ktot = sum(d.src[i].c_len for i in range(d.nsrc))
@@ -202,23 +222,37 @@ class PlanBase:
         elems = pin * ktot + sum(pout * d.dst[i].n_len * (2 if d.dst[i].accumulate else 1) for i in range(d.ndst))
         if d.mask_src:
             elems += pout * d.N
-        meta = {"kind": f"igemm_{tag}<{d.KH}x{d.KW}s{d.stride}>", "bytes": elems * es + taps * ktot * d.N * es,
-                "flops": 2 * pout * d.N * ktot * taps, "tag": f"{name} K={ktot} N={d.N} M={pout}"}
+        return {"kind": f"igemm_{tag}<{d.KH}x{d.KW}s{d.stride}{variant}>", "bytes": elems * es + taps * ktot * d.N * es,
+                "flops": 2 * pout * d.N * ktot * taps}, ktot, pout
+
+    def _conv(self, ll, d, tag, name=""):
+        self.keep.append(d)
+        meta, ktot, pout = self._conv_meta(d, tag)
+        meta["tag"] = f"{name} K={ktot} N={d.N} M={pout}"
         ll.add("ksmi_conv_forward", lambda: (C.byref(d), self.dt), meta)
+
+    def _wgrad_meta(self, d):
+        """... of one ksmi_conv_wgrad launch (the gradient leaves in fp32)"""
+        taps, es = d.KH * d.KW, self._es()
+        ktot = sum(d.src[i].c_len for i in range(d.nsrc))
+        pin, pout = d.B * d.Hin * d.Win, d.B * d.Hout * d.Wout
+        return {"kind": f"igemm_wgrad<{d.KH}x{d.KW}s{d.stride}>", "bytes": (pin * ktot + pout * d.N) * es + taps * ktot * d.N * 4,
+                "flops": 2 * pout * d.N * ktot * taps}, ktot, pout
+
+    def patch(self, desc, field, name):
+        """desc.field = address of scratch buffer `name`, once the scratch exists"""
+        self._later.append(lambda: setattr(desc, field, self.scr(name)))
 
     def _wgrad(self, d, ws, key, side_tag=None):
         if side_tag is None and self.side_tokens:
             self.bwd.add_wait_side(None)         # shares the split-slab scratch with the side-stream gradients
         self.keep.append(d)
         self.need("wgrad", ws)
-        self._later.append(lambda: setattr(d, "partial", self.scr("wgrad")))
-        taps, es = d.KH * d.KW, self._es()
-        ktot = sum(d.src[i].c_len for i in range(d.nsrc))
-        pin, pout = d.B * d.Hin * d.Win, d.B * d.Hout * d.Wout
-        meta = {"kind": f"igemm_wgrad<{d.KH}x{d.KW}s{d.stride}>", "bytes": (pin * ktot + pout * d.N) * es + taps * ktot * d.N * 4,
-                "flops": 2 * pout * d.N * ktot * taps, "tag": f"{key} K={ktot} N={d.N} M={pout}"}
+        self.patch(d, "partial", "wgrad")
+        meta, ktot, pout = self._wgrad_meta(d)
+        meta["tag"] = f"{key} K={ktot} N={d.N} M={pout}"
         if self.side_wgrad or side_tag is not None:
-            meta["side"] = True              # snunet_plan.LaunchList.run: eligible for the side stream
+            meta["side"] = True              # launch.LaunchList.run: eligible for the side stream
         if side_tag is not None:
             meta["side_tag"] = side_tag
         self.bwd.add("ksmi_conv_wgrad", lambda: (C.byref(d), self.dt), meta)
@@ -306,7 +340,7 @@ class PlanBase:
             elif fused == 2:
                 slot = self._rs_slot(dw.nsplit * N * 4)
                 dw.bias_grad = None
-                self._later.append(lambda: setattr(dw, "bias_grad", self.scr(slot)))
+                self.patch(dw, "bias_grad", slot)
             else:
                 dw.bias_grad = None
         self._wgrad(dw, ws, wkey, side_tag)

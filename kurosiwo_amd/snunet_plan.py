@@ -13,354 +13,12 @@ import os
 import torch
 
 from . import _lib
-from .runtime import DT, Act, SrcSpec, conv_grid_m, conv_npad, conv_stats_rows, make_conv, make_pack, make_wgrad, packed_weight_numel, stream_ptr
+from .plan_base import PlanBase, _Saved
+from .runtime import Act, SrcSpec, conv_npad, conv_stats_rows, make_conv, make_pack, make_wgrad, packed_weight_numel
 from .snunet import BN_EPS, BN_MOMENTUM
 
 
-_TAG_IDS = {}
-
-
-def _tag_id(tag):
-    """side-stream tags of the plans (arbitrary hashables) as the small integers ksmi_op carries"""
-    return _TAG_IDS.setdefault(tag, len(_TAG_IDS))
-
-
-def _sig_codes(argtypes):
-    """signature string of tools/gen_thunks.py: one letter per argument (p pointer, i int, u unsigned, l int64, z size_t, f float, d double)"""
-    out = []
-    for t in argtypes:
-        if t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and (issubclass(t, C._Pointer) or issubclass(t, C.Array))):
-            out.append("p")
-        else:
-            out.append({C.c_int: "i", C.c_int32: "i", C.c_uint32: "u", C.c_int64: "l", C.c_size_t: "z", C.c_float: "f", C.c_double: "d"}[t])
-    return "".join(out)
-
-
-def _slot(code, v, struct):
-    """one prepared argument as the 64-bit slot the call thunks read (include/ksmi.h ksmi_op)"""
-    if hasattr(v, "value") and not hasattr(v, "_obj"):        # a ctypes scalar (c_void_p, c_int, ...)
-        v = v.value
-    if code == "p":
-        if v is None:
-            return 0
-        if isinstance(v, int):
-            return v
-        if hasattr(v, "_obj"):                                # ctypes.byref(x)
-            return C.addressof(v._obj)
-        if isinstance(v, (C.Array, C.Structure)):
-            return C.addressof(v)
-        if isinstance(v, C._Pointer):
-            return C.cast(v, C.c_void_p).value or 0
-        raise _lib.KsmiError(f"launch list: cannot take the address of a {type(v).__name__} argument")
-    if code == "f":
-        return struct.unpack("<I", struct.pack("<f", float(v)))[0]
-    if code == "d":
-        return struct.unpack("<Q", struct.pack("<d", float(v)))[0]
-    return int(v) & 0xFFFFFFFFFFFFFFFF
-
-
-_PLAIN_RUNNERS = {}
-
-
-def _plain_runner(st):
-    """the executor state of single-stream runs (model(x) outside a train step): everything on the caller's current stream"""
-    dev = torch.cuda.current_device() if torch.cuda.is_available() else -1
-    lib = _lib.load()
-    r = _PLAIN_RUNNERS.get(dev)
-    if r is None:
-        r = _PLAIN_RUNNERS[dev] = C.c_void_p(lib.ksmi_runner_create())
-    lib.ksmi_runner_set_streams(r, st, None, None, None)
-    return r
-
-
-class LaunchList:
-    """(name, argfn, meta) triples; argfn() is evaluated once, after all scratch buffers exist.
-    meta = {"kind": kernel class, "bytes": algorithmic HBM bytes, "flops": 2*MAC} for the roofline, plus the scheduling tags
-    "lane" (compute lane the launch belongs to: 0 = the caller's stream, 1 = the second lane) and "side" (weight gradient: may
-    run on the side stream).  ("@wait", (a, b)) entries order lane b behind everything lane a was handed so far."""
-
-    def __init__(self):
-        self.pending, self.calls = [], []
-        self.cur_lane = 0
-        self.cur_stage = None      # measurement tag of the launches appended from here on (bench.py roofline.stages)
-
-    def add(self, name, argfn, meta=None):
-        meta = dict(meta) if meta else {"kind": name[5:], "bytes": 0, "flops": 0}
-        meta["lane"] = self.cur_lane
-        meta.setdefault("stage", self.cur_stage)
-        self.pending.append((name, argfn, meta))
-
-    def add_wait(self, src, dst):
-        self.pending.append(("@wait", lambda: (src, dst), {"kind": "wait", "bytes": 0, "flops": 0, "lane": dst}))
-
-    def add_allreduce(self, tensor_fn, meta=None):
-        """SyncBN (optional): SUM `tensor_fn()` (a small fp32 statistics tensor) over the ranks, in place, on the stream of
-        the issuing lane, between the launch that wrote it and the launch that reads it"""
-        m = {"kind": "syncbn_allreduce", "bytes": 0, "flops": 0, "lane": self.cur_lane}
-        m.setdefault("stage", self.cur_stage)
-        self.pending.append(("@allreduce", lambda: (tensor_fn(),), m | (meta or {})))
-
-    def add_wait_side(self, tag=None):
-        """the issuing lane waits for the side-stream launch that carries meta["side_tag"] == tag (None: for everything handed to the
-        side stream so far): placed before a launch that overwrites an operand of that weight gradient (plans that recycle buffers)"""
-        self.pending.append(("@wait_side", lambda: (tag,), {"kind": "wait", "bytes": 0, "flops": 0, "lane": self.cur_lane}))
-
-    def resolve(self, lib):
-        self.calls = [(None if name.startswith("@") else getattr(lib, name), tuple(argfn()), name, meta) for name, argfn, meta in self.pending]
-        self._compiled = None          # (the compiled form holds the argument values of the previous resolution)
-
-    # ---- compiled form (round 6): the list as an array of ksmi_op walked by ONE C-ABI call per segment (csrc/runlist.hip) instead of one
-    # ctypes call + stream switch + up to three torch event calls per launch in Python (host_issue_ms_per_step: 9 ms of a 14 ms SNUNet
-    # step, 29 of 34 ms for ChangeFormer).  The Python walk below stays for timed runs (a kernel timer brackets single launches), for hooks
-    # without an index list, for SyncBN's collectives, and as the cross-check (KSMI_RUN_LIST=0; tests/test_gpu_graph.py).
-    fast = os.environ.get("KSMI_RUN_LIST", "1") != "0"
-    _compiled = None
-
-    def _compile(self):
-        import struct
-        lib = _lib.load()
-        n = len(self.calls)
-        ops = (_lib.Op * max(n, 1))()
-        slots, where, skips, names, ok = [], [], [], [], True
-        for i, (fn, args, name, meta) in enumerate(self.calls):
-            op = ops[i]
-            op.tag, op.sig = -1, -1
-            op.lane = int(meta.get("lane", 0))
-            names.append(name)
-            if fn is None:
-                if name == "@wait":
-                    op.kind, op.a, op.b = _lib.OP_ORDER, int(args[0]), int(args[1])
-                elif name == "@wait_side":
-                    op.kind, op.tag = _lib.OP_WAIT_SIDE, (-1 if args[0] is None else _tag_id(args[0]))
-                else:
-                    ok = False                   # ("@allreduce": SyncBN's collectives are issued by torch.distributed)
-                continue
-            if name not in _lib.SIGNATURES:       # (a stubbed library in the host-only tests: the Python walk)
-                ok = False
-                continue
-            restype, argtypes = _lib.SIGNATURES[name]
-            codes = _sig_codes(argtypes[:-1])
-            sig = lib.ksmi_thunk_id(codes.encode())
-            if sig < 0 or len(codes) != len(args):
-                raise _lib.KsmiError(f"launch list: no call thunk for {name} ({codes!r}, {len(args)} arguments): re-run tools/gen_thunks.py")
-            op.kind, op.sig, op.nargs = _lib.OP_CALL, sig, len(args)
-            op.fn = C.cast(fn, C.c_void_p).value
-            op.side = (2 if meta.get("side_ix", 0) else 1) if meta.get("side") else 0
-            if op.side and meta.get("side_tag") is not None:
-                op.tag = _tag_id(meta["side_tag"])
-            where.append((i, len(slots)))
-            slots += [_slot(c, v, struct) for c, v in zip(codes, args)]
-            if meta.get("skip_if") is not None:
-                skips.append((i, meta["skip_if"]))
-        arr = (C.c_uint64 * max(len(slots), 1))(*slots)
-        base = C.addressof(arr)
-        for i, off in where:
-            ops[i].args = base + 8 * off
-        self._compiled = {"ops": ops, "slots": arr, "n": n, "skips": skips, "names": names, "ok": ok, "failed": C.c_int32(-1),
-                          "skipbuf": (C.c_uint8 * max(n, 1))() if skips else None}
-        return self._compiled
-
-    def _run_fast(self, hook, hook_at, streams):
-        cp = self._compiled
-        lib = _lib.load()
-        if streams is not None:
-            streams.begin()
-            runner = streams.runner()
-        else:
-            runner = _plain_runner(stream_ptr())
-        skip = None
-        if cp["skips"]:
-            skip = cp["skipbuf"]
-            for i, fn in cp["skips"]:
-                skip[i] = 1 if fn() else 0
-        n = cp["n"]
-        cuts = sorted({i + 1 for i in hook_at if 0 <= i < n} | {n}) if hook is not None else [n]
-        a = 0
-        for b in cuts:
-            rc = lib.ksmi_run_list(runner, cp["ops"], a, b, skip, C.byref(cp["failed"]))
-            if rc != 0:
-                at = cp["failed"].value
-                _lib.check(rc, cp["names"][at] if 0 <= at < n else "ksmi_run_list")
-            if hook is not None and (b - 1) in hook_at:
-                hook(b - 1)
-            a = b
-
-    def run(self, timer=None, hook=None, streams=None, hook_at=None):
-        """hook_at: the list indices at which `hook` has work to do (dp.BucketedAllReduce.hook_indices); with it (or without a hook) and
-        without a timer the compiled list runs (see above).
-        streams = StepStreams or None.  None: every launch on the current stream, in list order (always a valid order; the
-        "@wait" entries are no-ops).  With streams: launches of lane 1 go to the second compute stream, launches tagged "side" (the
-        weight gradients: nothing on the critical path of the backward pass reads them) to the side stream behind an event recorded
-        on the issuing lane's stream at that point of the list, so that independent work fills the machine next to the
-        bandwidth-bound BatchNorm / elementwise launches of the critical path; the caller joins (StepStreams.join) before
-        anything outside the lists reads the results."""
-        if (timer is None or not getattr(timer, "active", True)) and self.fast and self.calls and (hook is None or hook_at is not None):
-            cp = self._compiled or self._compile()
-            if cp["ok"]:
-                return self._run_fast(hook, hook_at or (), streams)
-        if streams is not None:
-            streams.begin()
-        st, cur = stream_ptr(), 0
-        try:
-            for idx, (fn, args, name, meta) in enumerate(self.calls):
-                if fn is None and name == "@allreduce":
-                    lane = meta["lane"] if streams is not None and streams.lanes else 0
-                    if lane != cur:
-                        torch.cuda.set_stream(streams.stream(lane))
-                        st, cur = stream_ptr(), lane
-                    from . import distributed as D
-                    D.all_reduce_sum_(args[0])                       # (stream-ordered on RCCL; gloo stages through the host)
-                    if hook is not None:
-                        hook(idx)
-                    continue
-                if fn is None:
-                    if name == "@wait_side":
-                        if streams is not None and streams.use_side:
-                            streams.wait_side(args[0])
-                    elif streams is not None and streams.lanes:
-                        streams.order(*args)
-                    if hook is not None:
-                        hook(idx)
-                    continue
-                if meta.get("skip_if") is not None and meta["skip_if"]():      # (plan_base: the bf16 mirror the optimiser just wrote)
-                    continue
-                lane = meta["lane"] if streams is not None and streams.lanes else 0
-                if lane != cur:
-                    torch.cuda.set_stream(streams.stream(lane))
-                    st, cur = stream_ptr(), lane
-                timed = timer is not None and timer.wants(meta["kind"])
-                if timed:
-                    timer.begin(meta["kind"], meta)
-                if streams is not None and streams.use_side and not timed and meta.get("side"):     # (a timed launch is bracketed by events on its lane's stream)
-                    six = meta.get("side_ix", 0)
-                    rc = fn(*args, streams.fork_side(six) if six else streams.fork_side())
-                    if meta.get("side_tag") is not None:
-                        streams.mark_side(meta["side_tag"], six) if six else streams.mark_side(meta["side_tag"])
-                else:
-                    rc = fn(*args, st)
-                if timed:
-                    timer.end()
-                if rc != 0:
-                    _lib.check(rc, name)
-                if hook is not None:
-                    hook(idx)
-        finally:
-            if cur != 0:
-                torch.cuda.set_stream(streams.main)
-
-
-class StepStreams:
-    """The HIP streams of one train step: main = the caller's current stream (lane 0), lane1 = a second compute lane for the
-    deeper decoder blocks (SNUNetPlan: they depend on the level-0 blocks only through the Up1_j edges), side = the weight gradients.
-    Cross-stream ordering is plain event record / wait pairs, so a step that uses them still captures into one HIP graph."""
-
-    def __init__(self, device, lanes=True, side=True):
-        self.side = torch.cuda.Stream(device=device)       # (stream priorities measured no better, DESIGN.md §5)
-        # KSMI_SIDE2=1 (experiment): a second side stream; the SNUNet plan alternates its weight gradients between the two by parameter
-        # (meta["side_ix"]: launches that accumulate into one gradient stay on one stream), so the slab reducer of one weight gradient
-        # runs beside the main kernel of the next
-        self.side2 = torch.cuda.Stream(device=device) if (side and os.environ.get("KSMI_SIDE2", "0") == "1") else None
-        self.side2_ptr = C.c_void_p(self.side2.cuda_stream) if self.side2 is not None else None
-        self.lane1 = torch.cuda.Stream(device=device) if lanes else None
-        self.lanes, self.use_side = bool(lanes), bool(side)
-        self.side_ptr = C.c_void_p(self.side.cuda_stream)
-        self.main = None
-        self.dirty = False
-        self.side_busy = False
-        self.events = {}           # side_tag -> event recorded behind that launch on the side stream (LaunchList.add_wait_side)
-
-    _runner = None
-
-    def begin(self):
-        if self.main is None:
-            self.main = torch.cuda.current_stream()
-            if self._runner is not None:
-                self._bind_runner()
-
-    def _bind_runner(self):
-        _lib.load().ksmi_runner_set_streams(self._runner, C.c_void_p(self.main.cuda_stream),
-                                            C.c_void_p(self.lane1.cuda_stream) if self.lanes else None,
-                                            self.side_ptr if self.use_side else None, self.side2_ptr if self.use_side else None)
-
-    def runner(self):
-        """executor state of the compiled launch lists (csrc/runlist.hip) bound to this step's streams; call after begin()"""
-        if self._runner is None:
-            self._runner = C.c_void_p(_lib.load().ksmi_runner_create())
-            self._bind_runner()
-        return self._runner
-
-    def __del__(self):
-        try:
-            if self._runner is not None:
-                _lib.load().ksmi_runner_destroy(self._runner)
-        except Exception:
-            pass
-
-    def stream(self, lane):
-        return self.main if lane == 0 else self.lane1
-
-    def _event(self, stream):
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        return ev
-
-    def order(self, src, dst):
-        self.stream(dst).wait_event(self._event(self.stream(src)))
-        self.dirty = True
-
-    def fork_side(self, ix=0):
-        two = ix and self.side2 is not None
-        (self.side2 if two else self.side).wait_event(self._event(torch.cuda.current_stream()))
-        self.dirty = self.side_busy = True
-        return self.side2_ptr if two else self.side_ptr
-
-    def mark_side(self, tag, ix=0):
-        self.events[tag] = self._event(self.side2 if (ix and self.side2 is not None) else self.side)
-
-    def wait_side(self, tag):
-        if tag is None:
-            if self.side_busy:                 # (nothing handed to the side stream since the last such wait: nothing to wait for)
-                torch.cuda.current_stream().wait_stream(self.side)
-                if self.side2 is not None:
-                    torch.cuda.current_stream().wait_stream(self.side2)
-                self.side_busy = False
-        elif tag in self.events:
-            torch.cuda.current_stream().wait_event(self.events.pop(tag))
-
-    def all_streams(self):
-        """every stream a launch of the step may have run on"""
-        return [s for s in (self.main, self.lane1 if self.lanes else None, self.side if self.use_side else None,
-                            self.side2 if self.use_side else None) if s is not None]
-
-    def join(self):
-        """the current stream waits for every other stream of the step"""
-        if self.dirty:
-            cur = torch.cuda.current_stream()
-            for s in (self.main, self.lane1, self.side, self.side2):
-                if s is not None and s.cuda_stream != cur.cuda_stream:
-                    cur.wait_stream(s)
-        if self.main is not None and torch.cuda.current_stream().cuda_stream == self.main.cuda_stream:
-            self.dirty = False
-
-    def end(self):
-        self.join()
-        if self._runner is not None:                 # (the compiled lists keep their own dirty / tag state: main joins the other streams)
-            _lib.check(_lib.load().ksmi_runner_join(self._runner), "ksmi_runner_join")
-        self.main = None
-        self.events.clear()
-        self.side_busy = False
-
-
-class _Saved:
-    """saved statistics of one BatchNorm call: rows = mean, rstd, scale, shift"""
-
-    def __init__(self, Cch, device):
-        self.t = torch.zeros((4, Cch), dtype=torch.float32, device=device)
-        self.mean, self.rstd, self.scale, self.shift = (self.t[i].data_ptr() for i in range(4))
-        self.scale_t, self.shift_t = self.t[2], self.t[3]
-
-
-class SNUNetPlan:
+class SNUNetPlan(PlanBase):
     side_wgrad = True          # weight gradients on the train step's side stream (see LaunchList.run; plan_base.PlanBase.side_wgrad)
     two_lanes = True           # the decoder launches carry lane tags and hand-over entries (StepStreams)
     bn_fused = os.environ.get("KSMI_BN_FUSED", "1") != "0"     # statistics finish inside the consuming pass (csrc/bnfused.hip)
@@ -368,9 +26,11 @@ class SNUNetPlan:
     up_gemm = os.environ.get("KSMI_UP_GEMM", "1") != "0"           # ConvTranspose2d(k2, s2) with C >= 128 as token GEMMs (ksmi_up_*)
     up_wgrad64 = os.environ.get("KSMI_UP_WGRAD64", "1") != "0"     # ... and the level-0 Up weight gradients (C = 64)
     up_wgrad128 = os.environ.get("KSMI_UP_WGRAD128", "1") != "0"   # ... and the level-1 ones (C = 128; after the reducer was parallelised)
+    pack_kind = "pack_weights_batched"
 
     def __init__(self, model, B, H, W, dtype, training, with_backward, tail=0, sync_bn=False):
-        self.m, self.B, self.H, self.W, self.dtype = model, B, H, W, dtype
+        self._init_lists(model, dtype, with_backward)        # (no bf16 parameter mirror: the convolutions read packed weights)
+        self.B, self.H, self.W = B, H, W
         # SyncBN (optional, SURVEY.md §8(e) "second-order items"): BatchNorm statistics of the GLOBAL batch -- the statistics rows of every
         # BatchNorm call (forward: sum, sum of squares; backward: sum g, sum g * xhat) are summed over the ranks before they are
         # finished, with the global pixel count.  Data parallelism with it equals one process on the whole batch
@@ -381,18 +41,11 @@ class SNUNetPlan:
         self.bn_world = _D.world_size() if self.sync_bn else 1
         if self.sync_bn:
             self.bn_fused = False
-        self.training, self.with_backward = training, with_backward
-        self.dev = model.flat_params.device
-        self.dt = DT[dtype]
-        self.lib = _lib.load()
-        self.packs, self.fwd, self.bwd = LaunchList(), LaunchList(), LaunchList()
-        self.keep = []
-        self._pinit = set()
-        self._pack_descs = []      # every weight-pack descriptor of the plan -> ONE batched launch per step
+        self.training = training
         self._up_packs = []        # (ConvTranspose weight, its [4C][C] bf16 image, C) of the `up` layers on the token-GEMM path
-        self.param_ready = {}      # parameter key -> index of the last backward launch writing its gradient
-        self._need, self._bufs, self._later = {}, {}, []
-        self._rowsums = []         # deferred row reductions (bias gradients): (RowsumDesc, parameter key) -> ONE launch ending the backward
+        # deferred row reductions (bias gradients): (RowsumDesc, parameter key) -> ONE launch ending the backward (PlanBase's batches of
+        # `rowsum_batch`, _rs_entries, stay empty here)
+        self._rowsums = []
         n, c = model.base_channel, model.in_channels
         self.n = n
         f = [n, 2 * n, 4 * n, 8 * n, 16 * n]
@@ -459,50 +112,36 @@ class SNUNetPlan:
                 self._lane(lane)
                 build()
             self._lane(0)
-            if self._rowsums:
-                import ctypes
-                nr = len(self._rowsums)
-                arr_r = (_lib.RowsumDesc * nr)(*[r for r, _ in self._rowsums])
-                raw_r = bytes(ctypes.string_at(ctypes.addressof(arr_r), ctypes.sizeof(arr_r)))
-                rtable = torch.frombuffer(bytearray(raw_r), dtype=torch.uint8).to(self.dev)
-                self.keep.append(rtable)
-                self.bwd.add("ksmi_reduce_rows_batched", lambda: (rtable.data_ptr(), nr))
-                self._mark(*[k for _, k in self._rowsums])
+        self._finish()
+
+    def _before_pack_table(self):
+        """the one row-sum launch that ends the backward list, and the weight images of the token-GEMM `up` layers"""
+        if self._rowsums:
+            nr = len(self._rowsums)
+            arr_r = (_lib.RowsumDesc * nr)(*[r for r, _ in self._rowsums])
+            raw_r = bytes(C.string_at(C.addressof(arr_r), C.sizeof(arr_r)))
+            rtable = torch.frombuffer(bytearray(raw_r), dtype=torch.uint8).to(self.dev)
+            self.keep.append(rtable)
+            self.bwd.add("ksmi_reduce_rows_batched", lambda: (rtable.data_ptr(), nr))
+            self._mark(*[k for _, k in self._rowsums])
         for i in range(0, len(self._up_packs), 16):           # KSMI_UP_PACK_MAX tensors per launch
             grp = self._up_packs[i:i + 16]
-            import ctypes
-            wt_a = (ctypes.c_void_p * len(grp))(*[w.data_ptr() for w, _, _ in grp])
-            wb_a = (ctypes.c_void_p * len(grp))(*[b.data_ptr() for _, b, _ in grp])
-            c_a = (ctypes.c_int * len(grp))(*[c for _, _, c in grp])
+            wt_a = (C.c_void_p * len(grp))(*[w.data_ptr() for w, _, _ in grp])
+            wb_a = (C.c_void_p * len(grp))(*[b.data_ptr() for _, b, _ in grp])
+            c_a = (C.c_int * len(grp))(*[c for _, _, c in grp])
             self.keep += [wt_a, wb_a, c_a]
             self.packs.add("ksmi_up_pack_weights_batched", lambda wt_a=wt_a, wb_a=wb_a, c_a=c_a, k=len(grp): (wt_a, wb_a, c_a, k),
                            {"kind": "up_pack_weight", "bytes": sum(4 * c * c * 6 for _, _, c in grp), "flops": 0})
-        # all weight packs of the step as one launch over a device-resident descriptor table
-        if self._pack_descs:
-            import ctypes
-            n = len(self._pack_descs)
-            arr = (_lib.PackDesc * n)(*self._pack_descs)
-            raw = bytes(ctypes.string_at(ctypes.addressof(arr), ctypes.sizeof(arr)))
-            table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.dev)
-            self.keep.append(table)
-            self.packs.add("ksmi_pack_weights_batched", lambda: (table.data_ptr(), n, self.dt))
-        # scratch allocation, descriptor patching, argument resolution
-        for name, nbytes in self._need.items():
-            self._bufs[name] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.dev)
-        for fn in self._later:
-            fn()
-        for ll in (self.packs, self.fwd, self.bwd):
-            ll.resolve(self.lib)
 
     # ---------------------------------------------------------------- helpers
     def _lane(self, lane):
         """launches appended from here on belong to compute lane `lane`"""
         self.fwd.cur_lane = self.bwd.cur_lane = lane
 
-    def _stage(self, H):
+    def _level(self, H):
         """measurement tag: the resolution level of the maps a module works on (L0 = full resolution ... L4 = 1/16)"""
         lvl = {self.H >> k: k for k in range(5)}.get(H)
-        self.fwd.cur_stage = self.bwd.cur_stage = None if lvl is None else f"L{lvl}"
+        self._stage(None if lvl is None else f"L{lvl}")
 
     def _sname(self, name):
         """scratch buffers that live from one launch to the next of the same block are per lane"""
@@ -515,37 +154,10 @@ class SNUNetPlan:
         a, b = back
         self.bwd_builders.append((0, lambda: self.bwd.add_wait(a, b)))
 
-    def need(self, name, nbytes):
-        self._need[name] = max(self._need.get(name, 0), int(nbytes))
-
-    def scr(self, name):
-        return self._bufs[name].data_ptr()
-
-    def patch(self, desc, field, name):
-        self._later.append(lambda: setattr(desc, field, self.scr(name)))
-
-    def _acc_param(self, key):
-        acc = 1 if key in self._pinit else 0
-        self._pinit.add(key)
-        return acc
-
-    def _packed(self, key, table, taps, N, n_mod, sK, sN, sD, sT, flip):
-        Npad = conv_npad(N)                          # (= ksmi_conv_desc.Npad of the layer: 32 columns below 16 channels, runtime.conv_npad)
-        out = torch.empty(packed_weight_numel(table, taps, Npad, self.dtype), dtype=self.dtype, device=self.dev)
-        d = make_pack(self.m._p(key), out, table, taps, N, Npad, n_mod, sK, sN, sD, sT, flip)
-        self.keep += [d, out]
-        self._pack_descs.append(d)
-        return out
-
     def _rows(self, npix):
         return max(1, min(512, npix // 256))
 
-    def _mark(self, *keys):
-        """the launch just appended to self.bwd is (so far) the last writer of these gradients"""
-        for k in keys:
-            self.param_ready[k] = len(self.bwd.pending) - 1
-
-    def _defer_rowsum(self, key, partial, rows, K, k, Cstride, Cc):
+    def _rowsum_at_end(self, key, partial, rows, K, k, Cstride, Cc):
         """grad[key][c] (+)= sum_rows partial[(r*K + k)*Cstride + c] in the batched launch that ends the backward; partial = None: zeros"""
         r = _lib.RowsumDesc()
         r.partial = partial.data_ptr() if partial is not None else None
@@ -559,21 +171,9 @@ class SNUNetPlan:
             self.keep.append(partial)
         self._rowsums.append((r, key))
 
-    def _es(self):
-        return 2 if self.dtype == torch.bfloat16 else 4
-
-    def _conv(self, ll, d, tag="fwd"):
+    def _conv(self, ll, d, tag="fwd", name=""):
         self.keep.append(d)
-        d.dir = 1 if "dgrad" in tag else 0            # (profiling tag: kernel names carry the direction, ksmi.h)
-        taps, es = d.KH * d.KW, self._es()
-        ktot = sum(d.src[i].c_len for i in range(d.nsrc))
-        pin, pout = d.B * d.Hin * d.Win, d.B * d.Hout * d.Wout
-        elems = pin * ktot + sum(pout * d.dst[i].n_len * (2 if d.dst[i].accumulate else 1) for i in range(d.ndst))
-        if d.mask_src:
-            elems += pout * d.N
-        nt = 2 if d.Npad >= 32 else 1
-        meta = {"kind": f"igemm_{tag}<{d.KH}x{d.KW}s{d.stride},BN{16 * nt}>", "bytes": elems * es + taps * ktot * d.N * es,
-                "flops": 2 * pout * d.N * ktot * taps}
+        meta, ktot, _ = self._conv_meta(d, tag, f",BN{32 if d.Npad >= 32 else 16}")
         meta["tag"] = f"K={ktot} N={d.N} {d.Hout}x{d.Wout} nsrc={d.nsrc}"
         ll.add("ksmi_conv_forward", lambda: (C.byref(d), self.dt), meta)
 
@@ -588,24 +188,21 @@ class SNUNetPlan:
             self._side_of[key] = len(self._side_of) & 1
         return self._side_of[key]
 
-    def _wgrad(self, d, ws, *keys):
+    def _wgrad(self, d, ws, key, side_tag=None):
+        assert side_tag is None              # (tagged waits are the token plans' scheme: nothing here overwrites a weight gradient's operands)
         self.keep.append(d)
         # the partial-slab scratch is per compute lane: with the side stream off (or a timed launch) the weight gradients of the two
         # lanes run concurrently on their lanes' streams (and per side stream: two weight gradients in flight own two slabs)
-        six = self._side_ix(keys[0]) if keys else 0
+        six = self._side_ix(key)
         sW = self._sname("wgrad" + ("_s2" if six else ""))
         self.need(sW, ws)
         self.patch(d, "partial", sW)
-        taps, es = d.KH * d.KW, self._es()
-        ktot = sum(d.src[i].c_len for i in range(d.nsrc))
-        pin, pout = d.B * d.Hin * d.Win, d.B * d.Hout * d.Wout
-        meta = {"kind": f"igemm_wgrad<{d.KH}x{d.KW}s{d.stride}>", "bytes": (pin * ktot + pout * d.N) * es + taps * ktot * d.N * 4,
-                "flops": 2 * pout * d.N * ktot * taps}
-        meta["tag"] = f"{keys[0] if keys else '?'} K={ktot} N={d.N} {d.Hout}x{d.Wout}"
+        meta, ktot, _ = self._wgrad_meta(d)
+        meta["tag"] = f"{key} K={ktot} N={d.N} {d.Hout}x{d.Wout}"
         meta["side"] = True                  # off the critical path: eligible for the side stream (LaunchList.run)
         meta["side_ix"] = six
         self.bwd.add("ksmi_conv_wgrad", lambda: (C.byref(d), self.dt), meta)
-        self._mark(*keys)
+        self._mark(key)
 
     # ---------------------------------------------------------------- "virtual sum" input gradient
     def _emit_dgrad(self, act, bias_key=None, gate=None):
@@ -656,14 +253,14 @@ class SNUNetPlan:
             rows_g = conv_stats_rows(d, self.dtype)
             st = torch.empty(rows_g * 2 * Npad, dtype=torch.float32, device=self.dev)
             d.stats = st.data_ptr()
-            self._defer_rowsum(bias_key, st, rows_g, 2, 0, Npad, Cc)
+            self._rowsum_at_end(bias_key, st, rows_g, 2, 0, Npad, Cc)
         self._conv(self.bwd, d, "dgrad")
         return gated if gated is not None else True
 
     # ---------------------------------------------------------------- nn.MaxPool2d(2,2)  (snunet.py:73)
     def _pool(self, x, name):
         y = Act(name, x.B, x.H // 2, x.W // 2, x.C, self.dtype, self.dev)
-        self._stage(x.H)
+        self._level(x.H)
         self.fwd.add("ksmi_maxpool2x2_forward", lambda: (x.t.data_ptr(), y.t.data_ptr(), x.B, x.H, x.W, x.C, self.dt))
         self._pool_bwd(x, y)
         return y
@@ -679,7 +276,7 @@ class SNUNetPlan:
     def _pool_bwd(self, x, y):
         """backward of y = maxpool2x2(x) (y written by ksmi_maxpool2x2_forward or by the fused block tail)"""
         def build_bwd():
-            self._stage(x.H)
+            self._level(x.H)
             self._emit_dgrad(y)
             acc = x.take_acc_flag()
             gy, gx = y.grad(), x.grad()
@@ -699,7 +296,7 @@ class SNUNetPlan:
     def _up(self, name, x):
         Cc, B, H, W = x.C, x.B, x.H, x.W
         y = Act(name, B, 2 * H, 2 * W, Cc, self.dtype, self.dev)
-        self._stage(2 * H)                                   # (an Up is booked on the level it writes)
+        self._level(2 * H)                                   # (an Up is booked on the level it writes)
         wkey, bkey = f"{name}.up.weight", f"{name}.up.bias"
         # levels with C >= 128 (Up2_j, Up3_j, Up4_0): the transposed convolution and both of its gradients as token GEMMs over the
         # "depth rows" of the output (csrc/gemm2.hip, ksmi_up_*): 400-600 TFLOP/s kernels instead of the 140-240 TFLOP/s the k2 s2
@@ -723,7 +320,7 @@ class SNUNetPlan:
             self._up_conv_forward(x, y, wkey, bkey, B, H, W, Cc)
 
         def build_bwd():
-            self._stage(2 * H)
+            self._level(2 * H)
             fused_bias = self._emit_dgrad(y, bias_key=bkey)
             gy = y.grad()
             s2 = [SrcSpec(gy, Cc)]
@@ -759,7 +356,7 @@ class SNUNetPlan:
                 rows = self._rows(npix)
                 pb = torch.empty(rows * Cc, dtype=torch.float32, device=self.dev)
                 self.bwd.add("ksmi_channel_sum", lambda: (gy.data_ptr(), pb.data_ptr(), rows, npix, Cc, self.dt))
-                self._defer_rowsum(bkey, pb, rows, 1, 0, Cc, Cc)
+                self._rowsum_at_end(bkey, pb, rows, 1, 0, Cc, Cc)
         self.bwd_builders.append((self.fwd.cur_lane, build_bwd))
         return y
 
@@ -770,7 +367,7 @@ class SNUNetPlan:
         m, B, H, W, Cc = self.m, out.B, out.H, out.W, out.C
         npix = B * H * W
         dtype, dt, training = self.dtype, self.dt, self.training
-        self._stage(H)
+        self._level(H)
         i_act = Act(f"{name}{branch}.i", B, H, W, Cc, dtype, self.dev)
         z_act = Act(f"{name}{branch}.z", B, H, W, Cc, dtype, self.dev)
         sv1, sv2 = _Saved(Cc, self.dev), _Saved(Cc, self.dev)
@@ -864,7 +461,7 @@ class SNUNetPlan:
 
         # ---- backward ----------------------------------------------------------------------------
         def build_bwd():
-            self._stage(H)
+            self._level(H)
             # (the virtual-sum input gradient below is the last writer of d out: the other producers -- pool / Up input gradients, the
             # ECAM head -- belong to modules later in the forward order, i.e. earlier in this list)
             gated = self._emit_dgrad(out, gate=(out.t, z_act.t, sv2)) if os.environ.get("KSMI_NO_GATE") is None else self._emit_dgrad(out)
@@ -915,11 +512,11 @@ class SNUNetPlan:
             # conv2.bias feeds a train-mode BatchNorm: its gradient sum(dz) is analytically 0 (the reference holds
             # ~1e-6 of rounding noise there); write exact zeros instead of two reduction launches.
             if training:
-                self._defer_rowsum(f"{name}.conv2.bias", None, 0, 1, 0, Cc, Cc)
+                self._rowsum_at_end(f"{name}.conv2.bias", None, 0, 1, 0, Cc, Cc)
             else:                                                   # eval-mode BN: d bias = sum(dz)
                 pz = torch.empty(rows * Cc, dtype=torch.float32, device=self.dev)
                 self.bwd.add("ksmi_channel_sum", lambda: (dz.data_ptr(), pz.data_ptr(), rows, npix, Cc, dt))
-                self._defer_rowsum(f"{name}.conv2.bias", pz, rows, 1, 0, Cc, Cc)
+                self._rowsum_at_end(f"{name}.conv2.bias", pz, rows, 1, 0, Cc, Cc)
             # dgrad of conv2 with fused ReLU mask + BN1-backward statistics in the epilogue
             dg2, tg2 = make_conv([SrcSpec(dz, Cc)], [(r, Cc, 0, 0, Cc, 0)], dz, None, None, B, H, W, H, W, 3, 3, 1, 1, Cc, dtype,
                                  mask=(i_act.t, sv1.t[0], sv1.t[1], sv1.t[2], sv1.t[3]))
@@ -951,11 +548,11 @@ class SNUNetPlan:
                                                                    pb1.data_ptr(), rows_b, float(npix), npix, Cc, dt),
                              {"kind": "bn_bwd_fin_apply_add", "bytes": npix * Cc * self._es() * 4, "flops": 0})
                 self._mark(f"{name}.bn1.weight", f"{name}.bn1.bias")
-                self._defer_rowsum(f"{name}.conv1.bias", pb1, rows_b, 1, 0, Cc, Cc)
+                self._rowsum_at_end(f"{name}.conv1.bias", pb1, rows_b, 1, 0, Cc, Cc)
             else:
                 self.bwd.add("ksmi_bn_bwd_apply_add", lambda: (r.data_ptr(), gout, i_act.t.data_ptr(), sv1.mean, sv1.rstd,
                                                                P("bn1.weight"), s1p, pb1.data_ptr(), rows, gcount, npix, Cc, dt))
-                self._defer_rowsum(f"{name}.conv1.bias", pb1, rows, 1, 0, Cc, Cc)
+                self._rowsum_at_end(f"{name}.conv1.bias", pb1, rows, 1, 0, Cc, Cc)
             a_w1 = self._acc_param(f"{name}.conv1.weight")
             if first:
                 # dW[n][c*9+t] = sum_px im2col[px][c*9+t] * di[px][n]  (1x1 weight-gradient GEMM over the saved im2col)
@@ -987,7 +584,7 @@ class SNUNetPlan:
         m, B, n = self.m, self.B, self.n
         HW = self.H * self.W
         dev, dt = self.dev, self.dt
-        self.fwd.cur_stage = self.bwd.cur_stage = "head"
+        self._stage("head")
         f32 = dict(dtype=torch.float32, device=dev)
         avg, mx = torch.zeros((B, 5 * n), **f32), torch.zeros((B, 5 * n), **f32)
         argmax = torch.zeros((B, 5 * n), dtype=torch.int32, device=dev)
@@ -1010,7 +607,7 @@ class SNUNetPlan:
                      {"kind": "ecam_final_forward", "bytes": 4 * T0 + B * HW * 3 * 4, "flops": 2 * B * HW * 4 * n * 3})
 
         def build_bwd():
-            self.fwd.cur_stage = self.bwd.cur_stage = "head"
+            self._stage("head")
             dca, dca1 = torch.zeros((B, 4 * n), **f32), torch.zeros((B, n), **f32)
             davg, dmax = torch.zeros((B, 5 * n), **f32), torch.zeros((B, 5 * n), **f32)
             ws_b = torch.empty(self.lib.ksmi_ecam_bwd_workspace(B, HW, n, 3), dtype=torch.uint8, device=dev)

@@ -10,6 +10,7 @@ import torch.distributed as dist
 
 from . import _lib
 from .dp import BucketedAllReduce, default_grad_dtype, make_buckets
+from .launch import StepStreams
 from .optim import FusedAdam
 from .runtime import stream_ptr
 
@@ -31,31 +32,17 @@ def _optimizer_step(step, mf, plan):
         opt.step_arena(*args)
 
 
-class _PlanTrainStep:
-    """zero_grad -> forward -> criterion -> backward (+ bucketed all-reduce) -> optimizer.step over a model plan."""
+class _StepBase:
+    """What every train step does around the launch lists of its plan: the optimiser and the bucketed gradient all-reduce, the streams
+    of the step, and the tail backward (+ bucket hooks) -> join -> reducer.wait -> optimizer.step."""
 
-    def __init__(self, model, plan, B, H, W, loss_function="ce+dice", class_weights=(1.0, 1.0, 1.0), optimizer=None, lr=1e-3,
-                 bucket_mb=8.0, group=None, graph=False, overlap_wgrad=True, overlap_lanes=True, grad_dtype=None, dp_mode=None):
-        if loss_function not in ("ce+dice", "cross_entropy") and loss_function not in _SEG_LOSS_KINDS:
-            raise NotImplementedError(loss_function)
-        self.model = model
+    def _init_step(self, model, plan, optimizer, lr, bucket_mb, group, grad_dtype, dp_mode):
+        self.model, self.plan = model, plan
         self.lib = _lib.load()
-        self.plan = plan
-        dev = self.plan.dev
-        self.B, self.HW = B, H * W
-        self.with_dice = 1 if loss_function == "ce+dice" else 0
-        self.seg_kind = _SEG_LOSS_KINDS.get(loss_function)      # None: the ce / ce+dice kernels of head.hip
-        self.cw = torch.tensor(list(class_weights), dtype=torch.float32, device=dev)
-        self.loss_out = torch.zeros(3, dtype=torch.float32, device=dev)
-        ws = self.lib.ksmi_loss_workspace(B, self.HW) if self.seg_kind is None else self.lib.ksmi_seg_loss_workspace(self.seg_kind, B, self.HW)
-        self.loss_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
-        self.labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
         self.optimizer = optimizer if optimizer is not None else FusedAdam(model.parameters(), lr=lr)
         n = model.flat_params.numel()
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        ready = {k: self.plan.param_ready.get(k, -1) for k in model._poff}
-        if os.environ.get("KSMI_DP_BUCKET_MB"):                        # A/B knob: gradient bucket size of the data-parallel all-reduce
-            bucket_mb = float(os.environ["KSMI_DP_BUCKET_MB"])
+        ready = {k: plan.param_ready.get(k, -1) for k in model._poff}
         buckets = make_buckets(ready, model._poff, None, n, int(bucket_mb * 1e6 / 4))
         self.grad_dtype = grad_dtype or default_grad_dtype(n)          # wire format of the gradient buckets (dp.py)
         self.reducer = BucketedAllReduce(model.flat_grads, buckets, group, self.grad_dtype if self.world > 1 or os.environ.get("KSMI_DP_FORCE") else "fp32",
@@ -64,26 +51,18 @@ class _PlanTrainStep:
         # of them (no compute stream is made to wait for another one because a bucket became ready)
         self.reducer.writer_streams = self._writer_streams
         self.timer = None          # optional kernel timer (bench.py)
-        self.use_graph = bool(graph) and self.world == 1     # replay the step as one captured HIP graph (configs["hip_graph"])
-        self.overlap_wgrad = bool(overlap_wgrad) and os.environ.get("KSMI_OVERLAP_WGRAD", "1") != "0"
-        self.overlap_lanes = bool(overlap_lanes) and os.environ.get("KSMI_OVERLAP_LANES", "1") != "0"
 
-    def _set_inputs(self, *inputs):
-        raise NotImplementedError
-
-    # ---- streams of the step (snunet_plan.StepStreams): the weight-gradient launches of the backward pass run on a side stream next to
-    # the bandwidth-bound BatchNorm launches of the critical path (overlap_wgrad; plans with side_wgrad), and the deeper decoder blocks
-    # of SNUNet on a second compute lane next to the level-0 column (overlap_lanes; plans with two_lanes).  Switches: the constructor
-    # arguments / configs["overlap_wgrad"], configs["overlap_lanes"] / KSMI_OVERLAP_WGRAD=0, KSMI_OVERLAP_LANES=0.
     _ss = None
 
+    def _stream_roles(self):
+        """(side stream for weight gradients?, second compute lane?) of the step as configured now"""
+        raise NotImplementedError
+
     def _streams(self):
-        side = self.overlap_wgrad and (getattr(self.plan, "side_wgrad", False) or getattr(self.plan, "side_tokens", False))
-        lanes = self.overlap_lanes and getattr(self.plan, "two_lanes", False)
+        side, lanes = self._stream_roles()
         if not (side or lanes):
             return None
         if self._ss is None or (self._ss.lanes, self._ss.use_side) != (lanes, side):
-            from .snunet_plan import StepStreams
             self._ss = StepStreams(self.plan.dev, lanes=lanes, side=side)
         return self._ss
 
@@ -97,10 +76,6 @@ class _PlanTrainStep:
         """bucket hook of the backward launch list (the reducer orders its collective behind every stream of the step itself)"""
         self.reducer.after_launch(idx)
 
-    def set_batch(self, *args):
-        self._set_inputs(*args[:-1])
-        self.labels.copy_(args[-1], non_blocking=True)
-
     def _timed(self, kind, fn):
         t = self.timer
         on = t is not None and t.wants(kind)
@@ -109,6 +84,53 @@ class _PlanTrainStep:
         fn()
         if on:
             t.end()
+
+    def _backward_and_update(self):
+        p, ss = self.plan, self._streams()
+        p.bwd.run(self.timer, self._after_launch if ss is not None else self.reducer.after_launch, ss, hook_at=self.reducer.hook_indices())
+        if ss is not None:
+            ss.end()
+        self.reducer.wait()
+        self._timed("optimizer", lambda: _optimizer_step(self, self.model, p))
+
+
+class _PlanTrainStep(_StepBase):
+    """zero_grad -> forward -> criterion -> backward (+ bucketed all-reduce) -> optimizer.step over a model plan."""
+
+    def __init__(self, model, plan, B, H, W, loss_function="ce+dice", class_weights=(1.0, 1.0, 1.0), optimizer=None, lr=1e-3,
+                 bucket_mb=8.0, group=None, graph=False, overlap_wgrad=True, overlap_lanes=True, grad_dtype=None, dp_mode=None):
+        if loss_function not in ("ce+dice", "cross_entropy") and loss_function not in _SEG_LOSS_KINDS:
+            raise NotImplementedError(loss_function)
+        if os.environ.get("KSMI_DP_BUCKET_MB"):                        # A/B knob: gradient bucket size of the data-parallel all-reduce
+            bucket_mb = float(os.environ["KSMI_DP_BUCKET_MB"])
+        self._init_step(model, plan, optimizer, lr, bucket_mb, group, grad_dtype, dp_mode)
+        dev = plan.dev
+        self.B, self.HW = B, H * W
+        self.with_dice = 1 if loss_function == "ce+dice" else 0
+        self.seg_kind = _SEG_LOSS_KINDS.get(loss_function)      # None: the ce / ce+dice kernels of head.hip
+        self.cw = torch.tensor(list(class_weights), dtype=torch.float32, device=dev)
+        self.loss_out = torch.zeros(3, dtype=torch.float32, device=dev)
+        ws = self.lib.ksmi_loss_workspace(B, self.HW) if self.seg_kind is None else self.lib.ksmi_seg_loss_workspace(self.seg_kind, B, self.HW)
+        self.loss_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+        self.labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
+        self.use_graph = bool(graph) and self.world == 1     # replay the step as one captured HIP graph (configs["hip_graph"])
+        self.overlap_wgrad = bool(overlap_wgrad) and os.environ.get("KSMI_OVERLAP_WGRAD", "1") != "0"
+        self.overlap_lanes = bool(overlap_lanes) and os.environ.get("KSMI_OVERLAP_LANES", "1") != "0"
+
+    def _set_inputs(self, *inputs):
+        raise NotImplementedError
+
+    # ---- streams of the step (launch.StepStreams): the weight-gradient launches of the backward pass run on a side stream next to
+    # the bandwidth-bound BatchNorm launches of the critical path (overlap_wgrad; plans with side_wgrad), and the deeper decoder blocks
+    # of SNUNet on a second compute lane next to the level-0 column (overlap_lanes; plans with two_lanes).  Switches: the constructor
+    # arguments / configs["overlap_wgrad"], configs["overlap_lanes"] / KSMI_OVERLAP_WGRAD=0, KSMI_OVERLAP_LANES=0.
+    def _stream_roles(self):
+        return (bool(self.overlap_wgrad and (getattr(self.plan, "side_wgrad", False) or getattr(self.plan, "side_tokens", False))),
+                bool(self.overlap_lanes and getattr(self.plan, "two_lanes", False)))
+
+    def set_batch(self, *args):
+        self._set_inputs(*args[:-1])
+        self.labels.copy_(args[-1], non_blocking=True)
 
     # ---- HIP graph: the step is a static launch list on one stream (no allocation, no host sync, device-side step counters and
     # random-stream state), so it can be captured once and replayed -- the CPU then issues ONE graph launch per step instead of
@@ -175,13 +197,7 @@ class _PlanTrainStep:
             self._timed("seg_loss_backward", lambda: _lib.check(lib.ksmi_seg_loss_backward(
                 k, p.logits.data_ptr(), self.labels.data_ptr(), self.cw.data_ptr(), _FOCAL_GAMMA, self.loss_ws.data_ptr(), None,
                 p.dlogits.data_ptr(), B, HW, 3, st), "seg_loss_backward"))
-        ss = self._streams()
-        p.bwd.run(t, self._after_launch if ss is not None else self.reducer.after_launch, ss, hook_at=self.reducer.hook_indices())
-        if ss is not None:
-            ss.end()
-        self.reducer.wait()
-        mf = self.model
-        self._timed("optimizer", lambda: _optimizer_step(self, mf, p))
+        self._backward_and_update()
 
     def step(self, *args):
         self.set_batch(*args)
@@ -224,40 +240,20 @@ class SegTrainStep(_PlanTrainStep):
         self.plan.x.copy_(x, non_blocking=True)
 
 
-class MAETrainStep:
+class MAETrainStep(_StepBase):
     """training/train_mae.py:62-122 on the MAE plan: step(image) = zero_grad -> mae(image) (fresh random permutation,
     models/mae.py:73) -> backward (+ bucketed all-reduce) -> Adam, as one launch sequence.  loss_out[0] = reconstruction loss."""
 
     def __init__(self, model, B, optimizer=None, lr=1e-5, bucket_mb=32.0, group=None, loss_scale=1.0, grad_dtype=None, dp_mode=None):
-        self.model, self.B = model, B
-        self.lib = _lib.load()
-        self.plan = model.plan(B, True)
-        self.optimizer = optimizer if optimizer is not None else FusedAdam(model.parameters(), lr=lr)
-        n = model.flat_params.numel()
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        ready = {k: self.plan.param_ready.get(k, -1) for k in model._poff}
-        self.grad_dtype = grad_dtype or default_grad_dtype(n)
-        self.reducer = BucketedAllReduce(model.flat_grads, make_buckets(ready, model._poff, None, n, int(bucket_mb * 1e6 / 4)), group,
-                                         self.grad_dtype if self.world > 1 or os.environ.get("KSMI_DP_FORCE") else "fp32", mode=dp_mode)
-        self.reducer.writer_streams = lambda: ([torch.cuda.current_stream()] if self._ss is None or self._ss.main is None
-                                               else self._ss.all_streams())
+        self.B = B
+        self._init_step(model, model.plan(B, True), optimizer, lr, bucket_mb, group, grad_dtype, dp_mode)
         self.loss_out = self.plan.loss
         self.plan.dloss.fill_(loss_scale)
-        self.timer = None
 
-    # the nn.Linear weight gradients of the transformer layers on a side stream (plan_base.PlanBase.side_tokens; KSMI_OVERLAP_WGRAD=0: off)
-    _ss = None
-
-    def _streams(self):
-        if not (getattr(self.plan, "side_tokens", False) and os.environ.get("KSMI_OVERLAP_WGRAD", "1") != "0"):
-            return None
-        if self._ss is None:
-            from .snunet_plan import StepStreams
-            self._ss = StepStreams(self.plan.dev, lanes=False, side=True)
-        return self._ss
-
-    def _after_launch(self, idx):
-        self.reducer.after_launch(idx)
+    def _stream_roles(self):
+        """the nn.Linear weight gradients of the transformer layers on a side stream (plan_base.PlanBase.side_tokens); KSMI_OVERLAP_WGRAD=0,
+        read at every step: off"""
+        return bool(getattr(self.plan, "side_tokens", False)) and os.environ.get("KSMI_OVERLAP_WGRAD", "1") != "0", False
 
     def set_batch(self, image, rand_indices=None):
         self.plan.x.copy_(image, non_blocking=True)
@@ -271,18 +267,7 @@ class MAETrainStep:
             p.idx.copy_(torch.rand(self.B, p.N, device=p.dev).argsort(dim=-1))
         p.packs.run(t)
         p.fwd.run(t)
-        ss = self._streams()
-        p.bwd.run(t, self._after_launch if ss is not None else self.reducer.after_launch, ss, hook_at=self.reducer.hook_indices())
-        if ss is not None:
-            ss.end()
-        self.reducer.wait()
-        mf = self.model
-        on = t is not None and t.wants("optimizer")
-        if on:
-            t.begin("optimizer")
-        _optimizer_step(self, mf, p)
-        if on:
-            t.end()
+        self._backward_and_update()
 
     def step(self, image, rand_indices=None):
         self.set_batch(image, rand_indices)

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from .changeformer_plan import BN_EPS, BN_MOMENTUM, CS, ChangeFormerPlan
 from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
-from .snunet_plan import _Saved
+from .plan_base import _Saved
 from .unet import DECODER_CHANNELS, LAYERS
 
 

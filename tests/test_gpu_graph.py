@@ -103,7 +103,7 @@ def _lane_case(family, B, S, overlap, graph):
                                           ("floodvit", False), ("floodvit", True), ("changeformer", False), ("changeformer", True)])
 def test_side_lane_equals_single_stream(family, graph):
     """trainer.py overlap_wgrad / overlap_lanes: the weight-gradient launches run on a side stream and SNUNet's deeper decoder blocks on a
-    second compute lane (snunet_plan.StepStreams); every kernel is deterministic, so a missing dependency edge would show up as a
+    second compute lane (launch.StepStreams); every kernel is deterministic, so a missing dependency edge would show up as a
     different trajectory -- it must equal the single-stream one bit for bit, eagerly and as a captured graph (fork / join become graph
     edges).  224 x 224 tiles: launches long enough to really overlap."""
     B, S = (16, 224) if family == "floodvit" else (4, 224)       # the ViT at the benchmark's token count (3152 rows)
@@ -163,10 +163,10 @@ def test_lanes_without_the_side_stream_equal_single_stream():
 
 @pytest.mark.parametrize("family", ["snunet", "floodvit", "changeformer", "unet"])
 def test_compiled_launch_list_equals_the_python_walk(family, monkeypatch):
-    """snunet_plan.LaunchList: the compiled list (ONE ksmi_run_list call per segment, csrc/runlist.hip: typed call thunks, event ring,
+    """launch.LaunchList: the compiled list (ONE ksmi_run_list call per segment, csrc/runlist.hip: typed call thunks, event ring,
     tagged side-stream events) issues the same launches on the same streams behind the same dependency edges as the Python walk
     (KSMI_RUN_LIST=0): multi-stream trajectories equal bit for bit, losses, gradients and parameters."""
-    from kurosiwo_amd import snunet_plan as sp
+    from kurosiwo_amd import launch as sp
     B, S = (16, 224) if family == "floodvit" else (4, 224)
     data = _batches(4, B, 2, S, 47)
     out = []

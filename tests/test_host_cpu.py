@@ -152,10 +152,10 @@ def test_shard_batch_python_lists_and_scalars():
 
 
 def test_launch_list_orders_side_stream_gradients_behind_tagged_waits(monkeypatch):
-    """snunet_plan.LaunchList / StepStreams without a GPU: a launch tagged "side" goes to the side stream behind a fork and leaves a mark
+    """launch.LaunchList / StepStreams without a GPU: a launch tagged "side" goes to the side stream behind a fork and leaves a mark
     under its side_tag; "@wait_side" entries make the issuing lane wait for exactly that mark (None: for the whole side stream, once);
     without streams every entry runs in list order on the current stream and the waits are no-ops."""
-    from kurosiwo_amd import snunet_plan as sp
+    from kurosiwo_amd import launch as sp
     monkeypatch.setattr(sp, "stream_ptr", lambda: "MAIN")         # (the current HIP stream: no GPU here)
 
     log = []
@@ -213,12 +213,106 @@ def test_launch_list_orders_side_stream_gradients_behind_tagged_waits(monkeypatc
     assert [(k, x) for k, x, _ in log] == [("a", 1), ("w", 2), ("a", 3), ("w", 4)] and all(st != "SIDE" for _, _, st in log)
 
 
+class _FakeStream:
+    """what StepStreams asks of a torch stream, recording instead of touching HIP"""
+    def __init__(self, name, log, handle):
+        self.name, self.log, self.cuda_stream = name, log, handle
+
+    def wait_event(self, ev):
+        self.log.append((self.name, "wait_event", ev))
+
+    def wait_stream(self, s):
+        self.log.append((self.name, "wait_stream", s.name))
+
+
+def _step_streams_without_a_gpu(monkeypatch, log):
+    """a launch.StepStreams (side stream on, one compute lane) whose streams and events are recorders; the executor state of a compiled
+    list is bound to null streams, so nothing of HIP is touched"""
+    import ctypes as C
+    from kurosiwo_amd import launch as sp
+    monkeypatch.setattr(sp, "stream_ptr", lambda: "MAIN")
+    main = _FakeStream("main", log, 0)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: main)
+    monkeypatch.setattr(sp.StepStreams, "_event", lambda self, stream: ("event", stream.name))
+    ss = object.__new__(sp.StepStreams)
+    ss.side, ss.side2, ss.lane1, ss.side_ptr, ss.side2_ptr = _FakeStream("side", log, 1), None, None, C.c_void_p(None), None
+    ss.lanes, ss.use_side, ss.main, ss.dirty, ss.side_busy, ss.events = False, True, None, False, False, {}
+    return sp, ss
+
+
+def test_one_step_streams_refuses_a_second_walker(monkeypatch):
+    """launch.StepStreams between begin() and end(): the walker (Python / compiled) that handed work to a side stream owns the
+    step's fork / tag state; a multi-stream list on the other walker raises instead of silently skipping a "@wait_side".
+    Single-stream lists (streams=None) and lists without side-stream work are not part of it, and end() frees the step."""
+    import ctypes as C
+    from kurosiwo_amd import _lib
+    log, calls = [], []
+    sp, ss = _step_streams_without_a_gpu(monkeypatch, log)
+
+    class Lib:
+        def ksmi_w(self, x, st):
+            calls.append((x, st))
+            return 0
+
+    py = sp.LaunchList()                               # a stubbed library: the Python walk
+    py.add("ksmi_w", lambda: (1,), {"kind": "wgrad", "bytes": 0, "flops": 0, "side": True, "side_tag": "t"})
+    py.add_wait_side("t")
+    py.resolve(Lib())
+    d = _lib.ConvDesc()
+    compiled = sp.LaunchList()                         # real entry points: the compiled walk (never reached: the claim comes first)
+    compiled.add("ksmi_conv_wgrad", lambda: (C.byref(d), 1), {"kind": "wgrad", "bytes": 0, "flops": 0, "side": True, "side_tag": "u"})
+    compiled.resolve(_lib.load())
+    plain = sp.LaunchList()                            # nothing for lane 1 or a side stream in it
+    plain.add_wait_side(None)
+    plain.resolve(_lib.load())
+
+    py.run(None, None, ss)
+    assert calls == [(1, ss.side_ptr)] and ss._walker == "Python"
+    assert ("main", "wait_event", ("event", "side")) in log          # the tagged wait saw the Python walk's own mark
+    with pytest.raises(_lib.KsmiError, match="Python walk.*compiled walk"):
+        compiled.run(None, None, ss)
+    plain.run(None, None, ss)                          # compiled, but claims nothing
+    assert plain._compiled is not None and ss._walker == "Python"
+    ss.end()
+    assert ss._walker is None and ss.main is None
+    # the other order: a compiled list first (its claim as LaunchList._run_fast places it), then the Python walk
+    ss.begin()
+    ss.claim("compiled")
+    with pytest.raises(_lib.KsmiError, match="compiled walk.*Python walk"):
+        py.run(None, None, ss)
+    assert len(calls) == 1
+    ss.end()
+    py.run(None, None, ss)                             # a new step: free again
+    assert len(calls) == 2
+
+
+def test_step_streams_join_reaches_the_runner(monkeypatch):
+    """StepStreams.join() joins both halves of a step's stream state: the Python walk's (wait_stream on every other stream) and the
+    compiled walk's (ksmi_runner_join); end() = join() + reset"""
+    from kurosiwo_amd import _lib
+    log, joined = [], []
+    sp, ss = _step_streams_without_a_gpu(monkeypatch, log)
+    lib = _lib.load()
+    real = lib.ksmi_runner_join
+    monkeypatch.setattr(lib, "ksmi_runner_join", lambda r: joined.append(r.value) or real(r))
+    ss.join()
+    assert joined == []                                # no compiled list ran on these streams: no runner
+    ss.begin()
+    r = ss.runner()
+    assert r.value and ss._runner is r
+    ss.dirty = True
+    ss.join()
+    assert joined == [r.value] and ("main", "wait_stream", "side") in log and not ss.dirty
+    ss.end()
+    assert joined == [r.value, r.value] and ss.main is None
+
+
 def test_mirror_freshness_and_skip_if_without_a_gpu(monkeypatch):
     """The bf16 operand copy of the parameters (plan_base.wb): the optimiser that wrote it marks it with the version counter of the
     fp32 arena; the cast launch of the NEXT forward is skipped iff no in-place torch operation touched a parameter since, and the mark
     is consumed by that one forward.  LaunchList honours meta["skip_if"].  conv_npad: 32 padded columns for the thin heads."""
     import torch
-    from kurosiwo_amd import plan_base as pb, snunet_plan as sp
+    from kurosiwo_amd import launch as sp, plan_base as pb
     from kurosiwo_amd.runtime import conv_npad
     assert [conv_npad(n) for n in (1, 2, 3, 15, 16, 17, 32, 48, 100)] == [32, 32, 32, 32, 16, 32, 32, 48, 112]
 

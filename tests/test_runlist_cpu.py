@@ -8,7 +8,7 @@ import struct
 import subprocess
 import sys
 
-from kurosiwo_amd import _lib, snunet_plan as sp
+from kurosiwo_amd import _lib, launch as sp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
