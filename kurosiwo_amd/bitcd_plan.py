@@ -7,104 +7,33 @@ per date.  Head: nearest x2, conv_pred, |f1 - f2|, bilinear x4, conv3x3 -> BN ->
 """
 import ctypes as C
 
-import os
-
 import torch
 
 from .bitcd import LAYERS
-from .changeformer_plan import CS
-from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
+from .conv_plan import CS
+from .runtime import SrcSpec
 from .plan_base import _Saved
-from .unet_plan import UnetPlan
+from .unet_plan import ResNetPlan
 
 
-class BitCDPlan(UnetPlan):
+class BitCDPlan(ResNetPlan):
     input_names = ("x1", "x2")
 
     def __init__(self, model, B, H, W, dtype, training, with_backward):
-        self._init_base(model, dtype, with_backward)
-        self.B, self.H, self.W, self.training = B, H, W, training
+        self._init_conv(model, B, H, W, dtype, training, with_backward)
         self.cin, self.nc = model.input_nc, model.output_nc
         self.x = torch.empty((2, B, self.cin, H, W), dtype=torch.float32, device=self.dev)
         self.xA, self.xB = self.x[0], self.x[1]
         self.logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=self.dev)
         self.dlogits = torch.empty_like(self.logits) if with_backward else None
-        self.const = torch.zeros((2, 512), dtype=torch.float32, device=self.dev)
-        self.const[1].fill_(1.0)
-        self._gbuf, self._gacc, self._bwd = {}, set(), []
-        self._build_bitcd()
-        if with_backward:
-            for f in reversed(self._bwd):
-                f()
-        self._finish()
-
-    # ---------------------------------------------------------------- conv1 7x7 s2 -> bn1 -> relu -> maxpool 3x3 s2 (one date)
-    def _stem(self, date):
-        B, H, W, dt = self.B, self.H, self.W, self.dt
-        H1, W1 = H // 2, W // 2
-        R1 = B * H1 * W1
-        kc = 32 if self.dtype == torch.bfloat16 else 16
-        Kreal = self.cin * 49
-        Kpad = -(-Kreal // kc) * kc
-        col, s0, f1 = self.buf(R1, Kpad), self.buf(R1, 64), self.buf(B, H1, W1, 64)
-        sv0 = _Saved(64, self.dev)
-        self.fwd.add("ksmi_im2col", lambda: (self.x[date].data_ptr(), col.data_ptr(), B, self.cin, H, W, H1, W1, 7, 7, 2, 3, Kpad, 1, dt),
-                     self._elt_meta("im2col", 2 * R1 * Kpad))
-        d, table = make_conv([SrcSpec(col, Kpad, k_real=Kreal)], [(s0, 64, 0, 0, 64, 0)], s0, None, None, 1, R1, 1, R1, 1, 1, 1, 1, 0, 64, self.dtype)
-        d.wpk = self._packed("resnet.conv1.weight", table, 1, 64, 64, 1, Kreal, 0, 0).data_ptr()
-        rows0 = conv_stats_rows(d, self.dtype) if self.training else conv_grid_m(d)   # (rows of the kernel that will run it: see changeformer_plan._conv3)
-        if self.training:
-            self.need("stats", rows0 * 2 * d.Npad * 4)
-            self._later.append(lambda: setattr(d, "stats", self.scr("stats")))
-        self._conv(self.fwd, d, "stem7x7", "resnet.conv1")
-        self._bn_finalize("resnet.bn1", sv0, rows0, d.Npad, 64, R1)
-        self._affine(self.fwd, s0, sv0, f1, R1, 64, 1)
-        H2, W2 = H1 // 2, W1 // 2
-        p = self.buf(B, H2, W2, 64)
-        # with a backward pass the forward records the window position of each first maximum (one byte per output element): the backward
-        # compares codes instead of re-reading up to four windows per input element (325 -> ~40 us at 112 x 112 x 64 x 32 images)
-        pidx = torch.empty(p.numel(), dtype=torch.uint8, device=self.dev) if self.with_backward and not os.environ.get("KSMI_MAXPOOL_GATHER") else None
-        if pidx is not None:
-            self.fwd.add("ksmi_maxpool3x3s2_forward_idx", lambda: (f1.data_ptr(), p.data_ptr(), pidx.data_ptr(), B, H1, W1, 64, dt),
-                         self._elt_meta("maxpool3", 2 * R1 * 64))
-        else:
-            self.fwd.add("ksmi_maxpool3x3s2_forward", lambda: (f1.data_ptr(), p.data_ptr(), B, H1, W1, 64, dt), self._elt_meta("maxpool3", 2 * R1 * 64))
-
-        def bwd():
-            df1, ds0 = self.gbuf(f1), self.buf(R1, 64)
-            dp = self.gbuf(p)
-            acc = self.gacc(f1)
-            if pidx is not None:
-                self.bwd.add("ksmi_maxpool3x3s2_backward_idx", lambda: (pidx.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
-                             self._elt_meta("maxpool3_bwd", 2 * R1 * 64 + R1 * 64 // 2 + R1 * 64 // 4))
-            else:
-                self.bwd.add("ksmi_maxpool3x3s2_backward", lambda: (f1.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
-                             self._elt_meta("maxpool3_bwd", 4 * R1 * 64))
-            self._bnrelu_bwd("resnet.bn1", df1, f1, s0, sv0, ds0, R1, 64)
-            self._linear_bwd("resnet.conv1", col, Kpad, "resnet.conv1.weight", None, ds0, 64, R1, None, k_real=Kreal)
-        self._bwd.append(bwd)
-        return p, H2, W2
-
-    def _absdiff(self, s1, s2, Cc, h, w):
-        B, dt = self.B, self.dt
-        n = B * h * w * Cc
-        dbuf = self.buf(B, h, w, Cc)
-        self.fwd.add("ksmi_absdiff_forward", lambda: (s1.data_ptr(), s2.data_ptr(), dbuf.data_ptr(), n, dt), self._elt_meta("absdiff", 3 * n))
-
-        def bwd():
-            dd, d1, d2 = self.gbuf(dbuf), self.gbuf(s1), self.gbuf(s2)
-            a1, a2 = self.gacc(s1), self.gacc(s2)
-            self.bwd.add("ksmi_absdiff_backward", lambda: (s1.data_ptr(), s2.data_ptr(), dd.data_ptr(), d1.data_ptr(), d2.data_ptr(), a1, a2, n, dt),
-                         self._elt_meta("absdiff_bwd", 5 * n))
-        self._bwd.append(bwd)
-        return dbuf
+        self._build_lists(self._build_bitcd)
 
     # ---------------------------------------------------------------- the graph
     def _backbone(self, date, stages=4, pred=None):
         """forward_single (bit_cd.py:780-797) of one date: stem, layer1..`stages`, nearest x2, conv_pred -> (prediction map, h, w).
         `pred`: destination of conv_pred (a view of a buffer both dates share), else a new buffer."""
         m, B, dt = self.m, self.B, self.dt
-        t, h, w = self._stem(date)
+        _, t, h, w = self._resnet_stem("resnet", self.x[date])
         cin = 64
         for li, (ch, stride) in enumerate(LAYERS[:stages]):
             for bi in range(2):
@@ -119,7 +48,7 @@ class BitCDPlan(UnetPlan):
         h2, w2 = 2 * h, 2 * w
         Pd = self.buf(B, h2, w2, 32) if pred is None else pred
         self._cv(self.fwd, "conv_pred", [SrcSpec(U, cin)], [(Pd, 32, 0, 0, 32, 0)], "conv_pred.weight", h2, w2, h2, w2, 3, 1, 1, 32, cin,
-                 bias=m._p("conv_pred.bias"))
+                 bkey="conv_pred.bias")
         self.named[f"pred_{date + 1}"] = Pd
 
         def bwd(t=t, U=U, Pd=Pd, h=h, w=w, h2=h2, w2=w2, cin=cin):
@@ -162,28 +91,12 @@ class BitCDPlan(UnetPlan):
         self.named["cls"] = y
         P = self.buf(B, H, W, CS)
         wk, bk = "classifier.3.weight", "classifier.3.bias"
-        self._cv(self.fwd, "classifier.3", [SrcSpec(y, 32)], [(P, CS, 0, 0, nc, 0)], wk, H, W, H, W, 3, 1, 1, nc, 32, bias=m._p(bk))
+        self._cv(self.fwd, "classifier.3", [SrcSpec(y, 32)], [(P, CS, 0, 0, nc, 0)], wk, H, W, H, W, 3, 1, 1, nc, 32, bkey=bk)
         HW = H * W
         self.fwd.add("ksmi_out_to_nchw", lambda: (P.data_ptr(), self.logits.data_ptr(), B, nc, CS, HW, 0, dt))
 
         def head_bwd():
-            dP = self.buf(B * HW, CS)
-            dy = self.gbuf(y)
-            self.gacc(y)
-            self.bwd.add("ksmi_dout_to_nhwc", lambda: (self.dlogits.data_ptr(), self.logits.data_ptr(), dP.data_ptr(), B, nc, CS, HW, 0, dt))
-            psrc = [SrcSpec(dP, CS, 0, CS, k_real=nc)]
-            self._conv3(self.bwd, "classifier.3", psrc, [(dy, 32, 0, 0, 32, 0)], wk, None, B, H, W, 32, nc, dgrad=True)
-            gview = m._g(wk)[8:]
-            self.keep.append(gview)
-            dw, ws = make_wgrad(psrc, y, 32, 0, 32, gview, 32 * 9, 9, -1, self._acc_param(wk), B, H, W, H, W, 3, 3, 1, 1, self.dtype)
-            self._wgrad(dw, ws, wk)
-            rr = max(1, min(512, B * HW // 256))
-            self.need("red", rr * CS * 4)
-            accb = self._acc_param(bk)
-            gb = m._g(bk).data_ptr()
-            self.bwd.add("ksmi_channel_sum", lambda: (dP.data_ptr(), self.scr("red"), rr, B * HW, CS, dt), self._elt_meta("channel_sum", B * HW * CS))
-            self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("red"), rr, 1, CS, nc, None, None, gb, accb))
-            self._mark(bk)
+            dy = self._class_head_bwd("classifier.3", wk, bk, y, 32)
             dz = self.buf(B, H, W, 32)
             self._bnrelu_bwd("classifier.1", dy, y, z, sv, dz, npix, 32)
             self._wg([SrcSpec(X, 32)], dz, 32, "classifier.0.weight", H, W, H, W, 3, 1, 1, 32)
@@ -195,13 +108,7 @@ class BitCDPlan(UnetPlan):
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, x1, x2):
-        if x1.data_ptr() != self.x[0].data_ptr():
-            self.x[0].copy_(x1)
-        if x2.data_ptr() != self.x[1].data_ptr():
-            self.x[1].copy_(x2)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
+        return self._run_forward(self.logits, (x1, self.xA), (x2, self.xB))
 
 
 class BitCDTransformerPlan(BitCDPlan):

@@ -13,26 +13,16 @@ import torch
 
 from . import _lib
 from .changeformer import DEPTHS, EMBED_DIMS, NUM_HEADS, SR_RATIOS
-from .plan_base import PlanBase, _Saved
-from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
+from .conv_plan import CS, ConvPlan, drop_threshold
+from .plan_base import _Saved
+from .runtime import SrcSpec, conv_grid_m, make_conv, make_wgrad, phase_taps_k4s2
 
-BN_EPS, BN_MOMENTUM = 1e-5, 0.1
-CS = 8            # channel stride of the 3-channel NHWC heads (vector-aligned pad channels)
 # random-stream sites of one encoder block (site id = 8 * global block index + one of these; oracle/rng_ref.py mirrors them)
 SITE_ATTN, SITE_PROJ, SITE_MLP1, SITE_MLP2, SITE_PATH_ATTN, SITE_PATH_MLP = range(6)
 NO_SITE = (0, 1.0, 0)
 
 
-def drop_threshold(p):
-    """(thr, inv_keep): an element is dropped when its 32-bit draw < thr = round(p * 2^32); kept ones are scaled by 1/(1-p)"""
-    if p <= 0.0:
-        return 0, 1.0
-    if p >= 1.0:
-        raise ValueError("drop probability must be < 1")
-    return min(0xFFFFFFFF, int(round(p * 4294967296.0))), 1.0 / (1.0 - p)
-
-
-class ChangeFormerPlan(PlanBase):
+class ChangeFormerPlan(ConvPlan):
     input_names = ("x1", "x2")
     # the encoder's nn.Linear / sr-conv weight gradients on the train step's side stream (plan_base.PlanBase.side_tokens; waits in
     # _encoder_stage_bwd).  KSMI_CF_SIDE_TOKENS=0: the single-stream list.
@@ -40,12 +30,11 @@ class ChangeFormerPlan(PlanBase):
     slab_bias_side = True      # (plan_base._linear_wgrad: +1.1 % here, profiles/r05_ab_slab_bias.txt)
 
     def __init__(self, model, B, H, W, dtype, training, with_backward):
-        self._init_base(model, dtype, with_backward)
         if H % 32 or W % 32:
             raise ValueError("H and W must be multiples of 32")
         if (H // 32) * (W // 32) != 49:
             raise _lib.KsmiError("ChangeFormerV6 (HIP): the attention kernel is specialised for 224x224 tiles (7x7 = 49 reduced keys)")
-        self.B, self.H, self.W, self.training = B, H, W, training
+        self._init_conv(model, B, H, W, dtype, training, with_backward, const_width=max(model.embedding_dim, 8))
         self.E, self.nc, self.cin = model.embedding_dim, model.output_nc, model.input_nc
         self.x = torch.empty((2 * B, self.cin, H, W), dtype=torch.float32, device=self.dev)
         self.xA, self.xB = self.x[:B], self.x[B:]
@@ -53,9 +42,6 @@ class ChangeFormerPlan(PlanBase):
         self.outputs = [torch.empty((B, self.nc, h, w), dtype=torch.float32, device=self.dev) for h, w in hs]
         self.logits = self.outputs[-1]
         self.dlogits = torch.empty_like(self.logits) if with_backward else None
-        self.const = torch.zeros((2, max(self.E, 8)), dtype=torch.float32, device=self.dev)   # row 0 zeros, row 1 ones
-        self.const[1].fill_(1.0)
-        self._bsteps = []
         # stochastic layers (changeformer.py:267-275: drop_rate = attn_drop_rate = drop_path_rate = 0.1, dpr = linspace(0, 0.1, 13));
         # train mode only, exactly as nn.Dropout / DropPath
         nblk = sum(DEPTHS)
@@ -68,10 +54,8 @@ class ChangeFormerPlan(PlanBase):
         self.rng_ptr = model.rng_state().data_ptr() if self.stochastic else None
         if self.stochastic:
             self.fwd.add("ksmi_rng_advance", lambda: (self.rng_ptr,))
-        self._build()
-        if with_backward:
-            self._build_backward()
-        self._finish()
+        self._bwd.append(self._build_backward)          # (one builder for the whole backward pass, not a closure per layer)
+        self._build_lists(self._build)
 
     # ---------------------------------------------------------------- helpers
     def _site(self, gi, site, p):
@@ -87,62 +71,6 @@ class ChangeFormerPlan(PlanBase):
         ll.add("ksmi_dropout_apply", lambda: (x.data_ptr(), None if resid is None else resid.data_ptr(), y.data_ptr(), rows, cols, rows_per_sample,
                                               el[0], el[1], el[2], path[0], path[1], path[2], self.rng_ptr, self.dt),
                self._elt_meta("dropout", (2 if resid is None else 3) * rows * cols))
-
-    def _stats_ptr(self):
-        return (lambda: self.scr("stats")) if self.training else (lambda: None)
-
-    def _conv3(self, ll, name, srcs, dsts, wkey, bkey, B, H, W, N, Ktot, relu_out=0, alpha=0.0, resid=None, stats=False,
-               mask=None, dgrad=False, tag=None):
-        """3x3 s1 p1 convolution.  dgrad=True packs W for the input gradient (K = output channels, flipped taps)."""
-        d, table = make_conv(srcs, dsts, dsts[0][0], self.m._p(bkey) if bkey else None, None, B, H, W, H, W, 3, 3, 1, 1, N, self.dtype,
-                             mask=mask, alpha=alpha, relu_out=relu_out, resid=resid)
-        if dgrad:      # element (k = n_out, tap', col = c_in) = W[n][c][flip(tap')]
-            d.wpk = self._packed(wkey, table, 9, N, N, N * 9, 9, 0, 1, 1).data_ptr()
-        else:          # element (k = c_in, tap, col = n_out) = W[n][c][tap]
-            d.wpk = self._packed(wkey, table, 9, N, N, 9, Ktot * 9, 0, 1, 0).data_ptr()
-        # statistics rows of the kernel that will run this descriptor (one per persistent workgroup on igemm3 / igemm4, one per M-tile on
-        # igemm2; recorded in d.stats_rows: with the tile kernel's count the dispatch kept every convolution WITH statistics off the ring
-        # kernel -- diff_c1.0 ran at 660 instead of ~1100 TFLOP/s until round 5)
-        rows = conv_stats_rows(d, self.dtype) if stats else conv_grid_m(d)
-        if stats:
-            self.need("stats", rows * 2 * d.Npad * 4)
-            self._later.append(lambda: setattr(d, "stats", self.scr("stats")))
-        self._conv(ll, d, tag or ("conv3x3_dgrad" if dgrad else "conv3x3"), name)
-        return rows, d.Npad
-
-    def _bn_finalize(self, key, sv, rows, cpad, Cc, count):
-        m, tr = self.m, self.training
-        g, b = m._p(f"{key}.weight").data_ptr(), m._p(f"{key}.bias").data_ptr()
-        rm, rv, nbt = m._b(f"{key}.running_mean").data_ptr(), m._b(f"{key}.running_var").data_ptr(), m._c(f"{key}.num_batches_tracked").data_ptr()
-        st = self._stats_ptr()
-        self.fwd.add("ksmi_bn_finalize", lambda: (st(), rows, cpad, Cc, float(count), g, b, rm, rv, nbt, BN_MOMENTUM, BN_EPS,
-                                                  1 if tr else 0, sv.mean, sv.rstd, sv.scale, sv.shift))
-
-    def _bn_backward(self, key, dy, r, sv, dv, rows, cpad, Cc, count, npix, relu_mask):
-        """sums (from the consumer's dgrad epilogue in scratch 'stats') -> dgamma, dbeta, dv"""
-        self.need("bnsum", 2 * Cc * 4)
-        gw, gb = self.m._g(f"{key}.weight").data_ptr(), self.m._g(f"{key}.bias").data_ptr()
-        a1, a2 = self._acc_param(f"{key}.weight"), self._acc_param(f"{key}.bias")
-        gamma = self.m._p(f"{key}.weight").data_ptr()
-        # the partial rows finish inside the apply pass where the gradient arrives already masked (bnfused.hip MODE 0, as the SNUNet plan
-        # since round 4): one launch instead of two; KSMI_BN_FUSED_FAMILIES=0 keeps the separate reduce_rows launch (A/B)
-        if relu_mask == 0 and os.environ.get("KSMI_BN_FUSED_FAMILIES", "1") != "0" and self.lib.ksmi_bn_fused_supported(Cc, cpad, self.dt):
-            self.bwd.add("ksmi_bn_bwd_fin_apply_gated", lambda: (self.scr("stats"), rows, cpad, self.scr("bnsum"), gw, gb, a1, dy.data_ptr(), r.data_ptr(),
-                                                                 sv.mean, sv.rstd, gamma, dv.data_ptr(), float(count), npix, Cc, self.dt),
-                         self._elt_meta("bn_bwd_apply", 3 * npix * Cc))
-            self._mark(f"{key}.weight", f"{key}.bias")
-            return
-        self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("stats"), rows, 2, cpad, Cc, self.scr("bnsum"), gw, gb, a1))
-        self._mark(f"{key}.weight", f"{key}.bias")
-        self.bwd.add("ksmi_bn_bwd_apply", lambda: (dy.data_ptr(), r.data_ptr(), sv.mean, sv.rstd, gamma, self.scr("bnsum"), dv.data_ptr(),
-                                                   relu_mask, float(count), npix, Cc, self.dt), self._elt_meta("bn_bwd_apply", 3 * npix * Cc))
-
-    def _nomask(self, r, sv):
-        """epilogue 'mask' tuple that only accumulates the BatchNorm-backward sums (sum dy, sum dy*rhat) without masking"""
-        return (r, sv.t[0], sv.t[1], self.const[0], self.const[1])
-
-    def _relumask(self, r):
-        return (r, self.const[0], self.const[1], self.const[1], self.const[0])
 
     # ---------------------------------------------------------------- encoder
     def _build(self):
@@ -308,14 +236,10 @@ class ChangeFormerPlan(PlanBase):
         fsrcs = [SrcSpec(scales[i]["up"], E) for i in (4, 3, 2, 1)]
         d, table = make_conv(fsrcs, [(F0, E, 0, 0, E, 0)], F0, m._p(f"{D}.linear_fuse.0.bias"), None, B, H1, W1, H1, W1, 1, 1, 1, 0, E, self.dtype)
         d.wpk = self._packed(f"{D}.linear_fuse.0.weight", table, 1, E, E, 1, 4 * E, 0, 0).data_ptr()
-        rowsF = conv_stats_rows(d, self.dtype) if self.training else conv_grid_m(d)   # (rows of the kernel that will run it: see changeformer_plan._conv3)
-        if self.training:
-            self.need("stats", rowsF * 2 * d.Npad * 4)
-            self._later.append(lambda: setattr(d, "stats", self.scr("stats")))
+        rowsF = self._attach_stats(d) if self.training else conv_grid_m(d)
         self._conv(self.fwd, d, "conv1x1", "linear_fuse.0")
         self._bn_finalize(f"{D}.linear_fuse.1", svF, rowsF, d.Npad, E, np1)
-        self.fwd.add("ksmi_affine", lambda: (F0.data_ptr(), svF.scale, svF.shift, Fb.data_ptr(), np1, E, 0, C.c_float(1.0), dt),
-                     self._elt_meta("bn_apply", 2 * np1 * E))
+        self._affine(self.fwd, F0, svF, Fb, np1, E, 0)
         self.named["fuse"] = Fb
         # convd2x -> dense_2x -> convd1x -> dense_1x -> change_probability
         X2, Ra, Y2 = self.buf(B, 2 * H1, 2 * W1, E), self.buf(B, 2 * H1, 2 * W1, E), self.buf(B, 2 * H1, 2 * W1, E)
@@ -342,10 +266,6 @@ class ChangeFormerPlan(PlanBase):
                     f"{D}.{name}.conv2.conv2d.bias", B, H, W, E, E, alpha=0.1, resid=(X, E))
 
     # ================================================================ backward
-    def _wgrad3(self, srcs, dy, dyC, N, wkey, B, H, W, Ktot):
-        dw, ws = make_wgrad(srcs, dy, dyC, 0, N, self.m._g(wkey), 9, Ktot * 9, 1, self._acc_param(wkey), B, H, W, H, W, 3, 3, 1, 1, self.dtype)
-        self._wgrad(dw, ws, wkey)
-
     def _res_block_bwd(self, name, X, R_, dY, H, W):
         """in: dY (gradient of the block output, buffer reused as dX on return)"""
         D, E, B = "TDec_x2", self.E, self.B
@@ -357,10 +277,10 @@ class ChangeFormerPlan(PlanBase):
         w2, b2 = f"{D}.{name}.conv2.conv2d.weight", f"{D}.{name}.conv2.conv2d.bias"
         w1, b1 = f"{D}.{name}.conv1.conv2d.weight", f"{D}.{name}.conv1.conv2d.bias"
         self._conv3(self.bwd, f"{name}.conv2", [SrcSpec(g2, E)], [(dR, E, 0, 0, E, 0)], w2, None, B, H, W, E, E, mask=self._relumask(R_), dgrad=True)
-        self._wgrad3([SrcSpec(R_, E)], g2, E, E, w2, B, H, W, E)
+        self._wg([SrcSpec(R_, E)], g2, E, w2, H, W, H, W, 3, 1, 1, E)
         self._bias_grad(g2, npix, E, b2)
         self._conv3(self.bwd, f"{name}.conv1", [SrcSpec(dR, E)], [(dY, E, 0, 0, E, 1)], w1, None, B, H, W, E, E, dgrad=True)
-        self._wgrad3([SrcSpec(X, E)], dR, E, E, w1, B, H, W, E)
+        self._wg([SrcSpec(X, E)], dR, E, w1, H, W, H, W, 3, 1, 1, E)
         self._bias_grad(dR, npix, E, b1)
 
     def _build_backward(self):
@@ -431,13 +351,13 @@ class ChangeFormerPlan(PlanBase):
             w0, b0 = f"{D}.diff_c{i}.0.weight", f"{D}.diff_c{i}.0.bias"
             rows, cpad = self._conv3(self.bwd, f"diff_c{i}.3", [SrcSpec(dv2, E)], [(dy1, E, 0, 0, E, 0)], w3, None, B, h, w, E, E,
                                      mask=self._nomask(r1, sv), stats=True, dgrad=True)
-            self._wgrad3([SrcSpec(r1, E, scale=sv.scale_t, shift=sv.shift_t, relu=0)], dv2, E, E, w3, B, h, w, E)
+            self._wg([SrcSpec(r1, E, scale=sv.scale_t, shift=sv.shift_t, relu=0)], dv2, E, w3, h, w, h, w, 3, 1, 1, E)
             self._bias_grad(dv2, npix, E, b3)
             self._bn_backward(f"{D}.diff_c{i}.2", dy1, r1, sv, dv1, rows, cpad, E, npix, npix, 1)
             dL = self.buf(ft["R"], E)
             self._conv3(self.bwd, f"diff_c{i}.0", [SrcSpec(dv1, E)], [(dL[:npix], E, 0, 0, E, 0), (dL[npix:], E, 0, E, E, 0)], w0, None,
                         B, h, w, 2 * E, E, dgrad=True)
-            self._wgrad3([SrcSpec(sc["LA"], E), SrcSpec(sc["LB"], E)], dv1, E, E, w0, B, h, w, 2 * E)
+            self._wg([SrcSpec(sc["LA"], E), SrcSpec(sc["LB"], E)], dv1, E, w0, h, w, h, w, 3, 1, 1, 2 * E)
             self._bias_grad(dv1, npix, E, b0)
             df = self.buf(ft["R"], ft["C"])
             self._linear_bwd(f"linear_c{i}", ft["f"], ft["C"], f"{D}.linear_c{i}.proj.weight", f"{D}.linear_c{i}.proj.bias", dL, E, ft["R"], df)
@@ -449,12 +369,6 @@ class ChangeFormerPlan(PlanBase):
         for st in (3, 2, 1, 0):
             self._encoder_stage_bwd(self.feats[st])
 
-    def _zero_grad_key(self, key):
-        g = self.m._g(key)
-        self._pinit.add(key)
-        self.bwd.add("ksmi_fill_zero", lambda: (g.data_ptr(), g.numel() * 4))
-        self._mark(key)
-
     def _deconv_bwd_stats(self, name, x, Cin, N, H, W, dout, dx, r, sv):
         """_deconv_bwd whose input-gradient epilogue also accumulates the BatchNorm-backward sums of the deconv input"""
         D, B = "TDec_x2", self.B
@@ -465,20 +379,12 @@ class ChangeFormerPlan(PlanBase):
         rows_total, first = 0, True
         for py in range(2):
             for px in range(2):
-                tap_map = []
-                for a in range(2):
-                    for b in range(2):
-                        tap_map.append((2 * a if py else 1 + 2 * a) * 4 + (2 * b if px else 1 + 2 * b))
                 d, table = make_conv(src, [(dx, Cin, 0, 0, Cin, 0 if first else 1)], dx, None, None, B, H, W, H, W, 2, 2, 1, py, Cin, self.dtype,
                                      mask=self._nomask(r, sv), pad_x=px, in_map=(2, 2, py, px, 2 * H, 2 * W))
-                d.wpk = self._packed(wkey, table, 4, Cin, Cin, 16, N * 16, 0, 1, 0, tap_map).data_ptr()
-                rows = conv_stats_rows(d, self.dtype)               # (one row per persistent workgroup on igemm4's 2 x 2 instance, per M-tile on igemm2)
-                off = rows_total * 2 * d.Npad * 4
-                rows_total += rows
-                self._later.append(lambda d=d, off=off: setattr(d, "stats", self.scr("stats") + off))
+                d.wpk = self._packed(wkey, table, 4, Cin, Cin, 16, N * 16, 0, 1, 0, phase_taps_k4s2(py, px, False)).data_ptr()
+                rows_total += self._attach_stats(d, rows_total * 2 * d.Npad * 4)
                 self._conv(self.bwd, d, "deconv_dgrad_phase", f"{name}.p{py}{px}")
                 first = False
-        self.need("stats", rows_total * 2 * d.Npad * 4)
         self._last_rows, self._last_cpad = rows_total, d.Npad
         self._deconv_wgrad(src, x, Cin, N, H, W, wkey, B)
         self._bias_grad(dout, B * 4 * H * W, N, bkey)
@@ -645,17 +551,4 @@ class ChangeFormerPlan(PlanBase):
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, x1, x2):
-        if x1.data_ptr() != self.xA.data_ptr():
-            self.xA.copy_(x1)
-        if x2.data_ptr() != self.xB.data_ptr():
-            self.xB.copy_(x2)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
-
-    def run_backward(self, dlogits=None):
-        if not self.with_backward:
-            raise _lib.KsmiError("plan was built without backward")
-        if dlogits is not None and dlogits.data_ptr() != self.dlogits.data_ptr():
-            self.dlogits.copy_(dlogits)
-        self.bwd.run()
+        return self._run_forward(self.logits, (x1, self.xA), (x2, self.xB))

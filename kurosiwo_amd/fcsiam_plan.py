@@ -16,61 +16,35 @@ import os
 
 import torch
 
-from .changeformer_plan import CS, drop_threshold
+from .conv_plan import CS, ConvPlan, drop_threshold
 from .fcsiam import DECODER, ENCODER
-from .runtime import SrcSpec, make_conv, make_wgrad
+from .runtime import SrcSpec, make_conv, make_wgrad, phase_taps_k3s2
 from .plan_base import _Saved
-from .unet_plan import UnetPlan
 
 LAYERS = [n for st in ENCODER for n, _ in st] + [n for _, _, ch in DECODER for n, _ in ch]     # Dropout2d site = 2 * index + date
 
 
-class FCSiamPlan(UnetPlan):
+class FCSiamPlan(ConvPlan):
     input_names = ("x1", "x2")
 
     side_wgrad = False         # measured: many short launches, the fork events cost more than the overlap returns (4346 -> 4214 tiles/s)
 
     def __init__(self, model, B, H, W, dtype, training, with_backward):
-        self._init_base(model, dtype, with_backward)
-        self.B, self.H, self.W, self.training = B, H, W, training
+        self._init_conv(model, B, H, W, dtype, training, with_backward)
         self.cin, self.nc, self.diff = model.input_nbr, model.label_nbr, model.diff
         self.x = torch.empty((2, B, self.cin, H, W), dtype=torch.float32, device=self.dev)
         self.xA, self.xB = self.x[0], self.x[1]
         self.logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=self.dev)       # the model output (softmax / log-softmax map)
         self.dlogits = torch.empty_like(self.logits) if with_backward else None
-        self.const = torch.zeros((2, 512), dtype=torch.float32, device=self.dev)
-        self.const[1].fill_(1.0)
-        self._gbuf, self._gacc, self._bwd, self._zeroed = {}, set(), [], set()
+        self._zeroed = set()
         p = float(model.drop2d) if training else 0.0
         self.thr, self.inv = drop_threshold(p)
         self.rng_ptr = model.rng_state().data_ptr() if self.thr else None
         if self.thr:
             self.fwd.add("ksmi_rng_advance", lambda: (self.rng_ptr,))
-        self._build_fcsiam()
-        if with_backward:
-            for f in reversed(self._bwd):
-                f()
-        self._finish()
+        self._build_lists(self._build_fcsiam)
 
     # ---------------------------------------------------------------- building blocks
-    def _bnrelu_bwd_scaled(self, bnkey, dout, out, z, sv, dz, npix, Cc):
-        """out = relu(bn(z)) * Dropout2d materialised: the plane scale 1/(1-p) is constant on the active set (read from out > 0),
-        so the BatchNorm + ReLU backward kernels run unchanged and alpha scales dz, dgamma, dbeta"""
-        rows = max(1, min(512, npix // 256))
-        self.need("bnp", rows * 2 * Cc * 4)
-        self.need("bnsum", 2 * Cc * 4)
-        gw, gb = self.m._g(f"{bnkey}.weight").data_ptr(), self.m._g(f"{bnkey}.bias").data_ptr()
-        a1, _ = self._acc_param(f"{bnkey}.weight"), self._acc_param(f"{bnkey}.bias")
-        gamma = self.m._p(f"{bnkey}.weight").data_ptr()
-        dt, alpha = self.dt, C.c_float(self.inv)
-        self.bwd.add("ksmi_bnrelu_bwd_reduce", lambda: (dout.data_ptr(), out.data_ptr(), z.data_ptr(), sv.mean, sv.rstd, self.scr("bnp"), rows, npix, Cc, dt),
-                     self._elt_meta("bnrelu_bwd_reduce", 3 * npix * Cc))
-        self.bwd.add("ksmi_reduce_rows_scaled", lambda: (self.scr("bnp"), rows, 2, Cc, Cc, self.scr("bnsum"), gw, gb, a1, alpha))
-        self._mark(f"{bnkey}.weight", f"{bnkey}.bias")
-        self.bwd.add("ksmi_bnrelu_bwd_apply_scaled", lambda: (dout.data_ptr(), out.data_ptr(), z.data_ptr(), sv.mean, sv.rstd, gamma, self.scr("bnsum"),
-                                                              dz.data_ptr(), float(npix), npix, Cc, alpha, dt),
-                     self._elt_meta("bnrelu_bwd_apply", 5 * npix * Cc))
-
     def _zero_bias(self, bkey):
         """a convolution bias followed directly by a train-mode BatchNorm has an analytically zero gradient"""
         if bkey not in self._zeroed:
@@ -90,7 +64,7 @@ class FCSiamPlan(UnetPlan):
                                      stats=self.training, dgrad=True)
         else:
             rows, cpad = self._cv(self.fwd, f"conv{name}", specs, [(z, Cout, 0, 0, Cout, 0)], wkey, h, w, h, w, 3, 1, 1, Cout, Ktot,
-                                  stats=self.training, bias=m._p(bkey))
+                                  stats=self.training, bkey=bkey)
         self._bn_finalize(bnkey, sv, rows, cpad, Cout, npix)
         site = 2 * LAYERS.index(name) + date
         self.fwd.add("ksmi_bn_relu_drop2d", lambda: (z.data_ptr(), sv.scale, sv.shift, out.data_ptr(), B, h * w, Cout, self.thr, C.c_float(self.inv), site,
@@ -100,7 +74,7 @@ class FCSiamPlan(UnetPlan):
         def bwd():
             dout = self.gbuf(out)
             dz = self.buf(B, h, w, Cout)
-            self._bnrelu_bwd_scaled(bnkey, dout, out, z, sv, dz, npix, Cout)
+            self._bnrelu_bwd(bnkey, dout, out, z, sv, dz, npix, Cout, alpha=self.inv)
             self._zero_bias(bkey)
             if transposed:
                 acc, off = self._acc_param(wkey), 0
@@ -138,21 +112,16 @@ class FCSiamPlan(UnetPlan):
         return y
 
     def _upconv(self, lvl, x, Cu, h, w):
-        """nn.ConvTranspose2d(Cu, Cu, 3, stride=2, padding=1, output_padding=1): y[2m+py][2n+px] as four 2x2 phase convolutions of x"""
+        """nn.ConvTranspose2d(Cu, Cu, 3, stride=2, padding=1, output_padding=1): y[2m+py][2n+px] as four 2x2 phase convolutions of x
+        (runtime.phase_taps_k3s2)"""
         m, B = self.m, self.B
         wkey, bkey = f"upconv{lvl}.weight", f"upconv{lvl}.bias"
         y = self.buf(B, 2 * h, 2 * w, Cu)
         for py in range(2):
             for px in range(2):
-                tap_map = []
-                for a in range(2):
-                    for b in range(2):
-                        ky = (1 if a == 0 else -1) if py == 0 else (2 if a == 0 else 0)
-                        kx = (1 if b == 0 else -1) if px == 0 else (2 if b == 0 else 0)
-                        tap_map.append(-1 if ky < 0 or kx < 0 else ky * 3 + kx)
                 d, table = make_conv([SrcSpec(x, Cu)], [(y, Cu, 0, 0, Cu, 0)], y, m._p(bkey), None, B, h, w, h, w, 2, 2, 1, 0, Cu, self.dtype,
                                      out_map=(2, 2, py, px, 2 * h, 2 * w))
-                d.wpk = self._packed(wkey, table, 4, Cu, Cu, Cu * 9, 9, 0, 1, 0, tap_map).data_ptr()
+                d.wpk = self._packed(wkey, table, 4, Cu, Cu, Cu * 9, 9, 0, 1, 0, phase_taps_k3s2(py, px)).data_ptr()
                 self._conv(self.fwd, d, "upconv_phase", f"upconv{lvl}.p{py}{px}")
 
         def bwd():
@@ -163,20 +132,6 @@ class FCSiamPlan(UnetPlan):
             self._bias_grad(dy, B * 4 * h * w, Cu, bkey)
         self._bwd.append(bwd)
         return y
-
-    def _absdiff(self, s1, s2, Cc, h, w):
-        B, dt = self.B, self.dt
-        n = B * h * w * Cc
-        dbuf = self.buf(B, h, w, Cc)
-        self.fwd.add("ksmi_absdiff_forward", lambda: (s1.data_ptr(), s2.data_ptr(), dbuf.data_ptr(), n, dt), self._elt_meta("absdiff", 3 * n))
-
-        def bwd():
-            dd, d1, d2 = self.gbuf(dbuf), self.gbuf(s1), self.gbuf(s2)
-            a1, a2 = self.gacc(s1), self.gacc(s2)
-            self.bwd.add("ksmi_absdiff_backward", lambda: (s1.data_ptr(), s2.data_ptr(), dd.data_ptr(), d1.data_ptr(), d2.data_ptr(), a1, a2, n, dt),
-                         self._elt_meta("absdiff_bwd", 5 * n))
-        self._bwd.append(bwd)
-        return dbuf
 
     # ---------------------------------------------------------------- the graph
     def _build_fcsiam(self):
@@ -225,26 +180,12 @@ class FCSiamPlan(UnetPlan):
         x12d = y
 
         def head_bwd():
-            dP = self.buf(B * HW, CS)
-            self.bwd.add("ksmi_dout_to_nhwc", lambda: (self.dlogits.data_ptr(), self.logits.data_ptr(), dP.data_ptr(), B, nc, CS, HW, act, dt))
-            psrc = [SrcSpec(dP, CS, 0, CS, k_real=nc)]
+            dP, psrc = self._class_dP(act)
             self._wg(psrc, x12d, 16, wk, H, W, H, W, 3, 1, 1, nc)
             self._cv(self.bwd, "conv11d.dgrad", psrc, [(self.gbuf(x12d), 16, 0, 0, 16, self.gacc(x12d))], wk, H, W, H, W, 3, 1, 1, 16, nc, tag="dgrad")
-            rr = max(1, min(512, B * HW // 256))
-            self.need("red", rr * CS * 4)
-            accb = self._acc_param(bk)
-            gb = m._g(bk).data_ptr()
-            self.bwd.add("ksmi_channel_sum", lambda: (dP.data_ptr(), self.scr("red"), rr, B * HW, CS, dt), self._elt_meta("channel_sum", B * HW * CS))
-            self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("red"), rr, 1, CS, nc, None, None, gb, accb))
-            self._mark(bk)
+            self._class_bias_bwd(dP, bk)
         self._bwd.append(head_bwd)
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, x1, x2):
-        if x1.data_ptr() != self.x[0].data_ptr():
-            self.x[0].copy_(x1)
-        if x2.data_ptr() != self.x[1].data_ptr():
-            self.x[1].copy_(x2)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
+        return self._run_forward(self.logits, (x1, self.xA), (x2, self.xB))

@@ -206,15 +206,4 @@ class FloodViTPlan(PlanBase):
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, x):
-        if x.data_ptr() != self.x.data_ptr():
-            self.x.copy_(x)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
-
-    def run_backward(self, dlogits=None):
-        if not self.with_backward:
-            raise _lib.KsmiError("plan was built without backward")
-        if dlogits is not None and dlogits.data_ptr() != self.dlogits.data_ptr():
-            self.dlogits.copy_(dlogits)
-        self.bwd.run()
+        return self._run_forward(self.logits, (x, self.x))

@@ -171,13 +171,7 @@ class MAEPlan(PlanBase):
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, img, rand_indices):
-        if img.data_ptr() != self.x.data_ptr():
-            self.x.copy_(img)
-        if rand_indices.data_ptr() != self.idx.data_ptr():
-            self.idx.copy_(rand_indices)
-        self.packs.run()
-        self.fwd.run()
-        return self.loss
+        return self._run_forward(self.loss, (img, self.x), (rand_indices, self.idx))
 
     def run_backward(self, dloss=None):
         if not self.with_backward:

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib
-from .runtime import DT, SrcSpec, conv_npad, make_conv, make_pack, make_wgrad, packed_weight_numel
+from .runtime import DT, SrcSpec, conv_npad, make_conv, make_pack, make_wgrad, packed_weight_numel, phase_taps_k4s2
 from .launch import LaunchList
 
 LN_EPS = 1e-5
@@ -116,6 +116,23 @@ class PlanBase:
             fn()
         for ll in (self.packs, self.fwd, self.bwd):
             ll.resolve(self.lib)
+
+    # ---------------------------------------------------------------- execution
+    def _run_forward(self, out, *pairs):
+        """(input, staging buffer) pairs: copy each input unless it already is its staging buffer, then the weight packs and the forward list"""
+        for src, dst in pairs:
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src)
+        self.packs.run()
+        self.fwd.run()
+        return out
+
+    def run_backward(self, dlogits=None):
+        if not self.with_backward:
+            raise _lib.KsmiError("plan was built without backward")
+        if dlogits is not None and dlogits.data_ptr() != self.dlogits.data_ptr():
+            self.dlogits.copy_(dlogits)
+        self.bwd.run()
 
     # ---------------------------------------------------------------- small helpers
     def _stage(self, name):
@@ -445,28 +462,21 @@ class PlanBase:
 
     # ---------------------------------------------------------------- ConvTranspose2d(k4, s2, p1)
     def _deconv(self, name, x, Cin, N, H, W, out, outC, prefix="head.", suffix="", B=None):
-        """out[B,2H,2W,outC][..., :N] = ConvTranspose2d(x) + bias as 4 phase convolutions with 2x2 taps:
-        out[2m+py] = sum_a x[m - pad + a] * W[ky],  pad = 1 - py,  ky = (3 - 2a) if py == 0 else (2 - 2a)."""
+        """out[B,2H,2W,outC][..., :N] = ConvTranspose2d(x) + bias as 4 phase convolutions with 2x2 taps (runtime.phase_taps_k4s2)"""
         wkey, bkey = f"{prefix}{name}{suffix}.weight", f"{prefix}{name}{suffix}.bias"
         B = self.B if B is None else B
         for py in range(2):
             for px in range(2):
-                tap_map = []
-                for a in range(2):
-                    for b in range(2):
-                        ky = 3 - 2 * a if py == 0 else 2 - 2 * a
-                        kx = 3 - 2 * b if px == 0 else 2 - 2 * b
-                        tap_map.append(ky * 4 + kx)
                 d, table = make_conv([SrcSpec(x, Cin)], [(out, outC, 0, 0, N, 0)], out, self.m._p(bkey), None,
                                      B, H, W, H, W, 2, 2, 1, 1 - py, N, self.dtype, pad_x=1 - px,
                                      out_map=(2, 2, py, px, 2 * H, 2 * W))
                 # Wt[c][n][ky][kx]: k = c, column = n
-                d.wpk = self._packed(wkey, table, 4, N, N, N * 16, 16, 0, 1, 0, tap_map).data_ptr()
+                d.wpk = self._packed(wkey, table, 4, N, N, N * 16, 16, 0, 1, 0, phase_taps_k4s2(py, px, True)).data_ptr()
                 self._conv(self.fwd, d, "deconv_phase", f"{name}.p{py}{px}")
 
     def _deconv_wgrad(self, src, x, Cin, N, H, W, wkey, B):
         """dW[c][n][ky][kx] = sum x[iy,ix,c] dOut[2iy-1+ky, 2ix-1+kx, n] as four 2x2 stride-1 weight-gradient GEMMs over the parity
-        sub-images of dOut (tap (a,b) of phase (py,px) <-> ky = 2a | 1+2a, kx = 2b | 1+2b), each writing its 4 of the 16 taps"""
+        sub-images of dOut (runtime.phase_taps_k4s2), each writing its 4 of the 16 taps"""
         acc = self._acc_param(wkey)
         if os.environ.get("KSMI_DECONV_WGRAD_4X4"):
             dw, ws = make_wgrad(src, x, Cin, 0, Cin, self.m._g(wkey), 16, N * 16, 1, acc, B, 2 * H, 2 * W, H, W, 4, 4, 2, 1, self.dtype)
@@ -474,9 +484,8 @@ class PlanBase:
             return
         for py in range(2):
             for px in range(2):
-                tap_off = [(2 * a if py else 1 + 2 * a) * 4 + (2 * b if px else 1 + 2 * b) for a in range(2) for b in range(2)]
                 dw, ws = make_wgrad(src, x, Cin, 0, Cin, self.m._g(wkey), 16, N * 16, 0, acc, B, H, W, H, W, 2, 2, 1, py, self.dtype,
-                                    pad_x=px, in_map=(2, 2, py, px, 2 * H, 2 * W), tap_off=tap_off)
+                                    pad_x=px, in_map=(2, 2, py, px, 2 * H, 2 * W), tap_off=phase_taps_k4s2(py, px, False))
                 self._wgrad(dw, ws, wkey)
 
     def _deconv_bwd(self, name, x, Cin, N, H, W, dout, doutC, dx, mask=None, prefix="head.", suffix="", B=None, stats=None):
@@ -499,22 +508,15 @@ class PlanBase:
                 d.wpk = self._packed(wkey, table, 16, Cin, Cin, 16, N * 16, 0, 1, 0).data_ptr()
                 self._conv(self.bwd, d, "deconv_dgrad", name)
             else:
-                # dIn[iy] = sum_ky dOut[2 iy - 1 + ky] W[ky]: split by the parity of the dOut row.  Even rows E[m] = dOut[2m]: taps a = 0,1
-                # read E[iy + a] with ky = 1 + 2a (pad 0); odd rows O[m] = dOut[2m+1]: taps read O[iy - 1 + a] with ky = 2a (pad 1).
-                # Four dense 2x2 stride-1 convolutions over the strided views (every M-tile row useful; the single 4x4 stride-2
-                # convolution is limited to 100-pixel patches by its 22x22 halo = 39 % of the 256-row tile), accumulated in dx.
+                # Four dense 2x2 stride-1 convolutions over the parity sub-images of dOut (runtime.phase_taps_k4s2; every M-tile row useful;
+                # the single 4x4 stride-2 convolution is limited to 100-pixel patches by its 22x22 halo = 39 % of the 256-row tile),
+                # accumulated in dx.
                 first = True
                 for py in range(2):
                     for px in range(2):
-                        tap_map = []
-                        for a in range(2):
-                            for b in range(2):
-                                ky = 2 * a if py else 1 + 2 * a
-                                kx = 2 * b if px else 1 + 2 * b
-                                tap_map.append(ky * 4 + kx)
                         d, table = make_conv(src, [(dx, Cin, 0, 0, Cin, 0 if first else 1)], dx, None, None, B, H, W, H, W, 2, 2, 1, py, Cin,
                                              self.dtype, mask=mk, pad_x=px, in_map=(2, 2, py, px, 2 * H, 2 * W))   # 0/1 mask on every partial = mask on the sum
-                        d.wpk = self._packed(wkey, table, 4, Cin, Cin, 16, N * 16, 0, 1, 0, tap_map).data_ptr()
+                        d.wpk = self._packed(wkey, table, 4, Cin, Cin, 16, N * 16, 0, 1, 0, phase_taps_k4s2(py, px, False)).data_ptr()
                         self._conv(self.bwd, d, "deconv_dgrad_phase", f"{name}.p{py}{px}")
                         first = False
         self._deconv_wgrad(src, x, Cin, N, H, W, wkey, B)

@@ -191,6 +191,28 @@ def conv_npad(N):
     return 32 if N < 16 else (N + 15) // 16 * 16
 
 
+def phase_taps_k4s2(py, px, transposed):
+    """Tap map (entry a * 2 + b -> ky * 4 + kx) of phase (py, px) of a k4 s2 p1 (de)convolution run as four 2x2 stride-1 convolutions.
+    transposed=True, the forward of ConvTranspose2d: out[2m+py] = sum_a x[m - pad + a] * W[ky],  pad = 1 - py,
+    ky = (3 - 2a) if py == 0 else (2 - 2a).
+    transposed=False, its input and weight gradients: dIn[iy] = sum_ky dOut[2 iy - 1 + ky] W[ky], split by the parity of the dOut row.
+    Even rows E[m] = dOut[2m]: taps a = 0,1 read E[iy + a] with ky = 1 + 2a (pad 0); odd rows O[m] = dOut[2m+1]: taps read O[iy - 1 + a]
+    with ky = 2a (pad 1)."""
+    if transposed:
+        k = lambda p, a: 3 - 2 * a if p == 0 else 2 - 2 * a
+    else:
+        k = lambda p, a: 2 * a if p else 1 + 2 * a
+    return [k(py, a) * 4 + k(px, b) for a in range(2) for b in range(2)]
+
+
+def phase_taps_k3s2(py, px):
+    """Tap map (entry a * 2 + b -> ky * 3 + kx, -1 = a missing tap, packed as zero) of phase (py, px) of the input gradient of a 3x3
+    stride-2 pad-1 convolution (= the forward of ConvTranspose2d(k3, s2, p1, output_padding 1)) as four 2x2 phase convolutions over dy
+    placed at (2m+py, 2n+px): per axis dx[2m] = dy[m] W[1] ; dx[2m+1] = dy[m] W[2] + dy[m+1] W[0]."""
+    k = lambda p, a: (1 if a == 0 else -1) if p == 0 else (2 if a == 0 else 0)
+    return [-1 if k(py, a) < 0 or k(px, b) < 0 else k(py, a) * 3 + k(px, b) for a in range(2) for b in range(2)]
+
+
 def make_conv(srcs, dsts, wpk, bias, stats, B, Hin, Win, Hout, Wout, KH, KW, stride, pad, N, dtype,
               mask=None, ps_cout=0, max_pix=256, pad_x=None, out_map=None, alpha=0.0, relu_out=0, resid=None, in_map=None):
     """dsts: list of (tensor, C, c_off, n_begin, n_len, accumulate).  mask: (tensor, mean, rstd, scale, shift).

@@ -636,21 +636,6 @@ class SNUNetPlan(PlanBase):
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, xA, xB, tail=None):
-        if xA.data_ptr() != self.xA.data_ptr():
-            self.xA.copy_(xA)
-        if xB.data_ptr() != self.xB.data_ptr():
-            self.xB.copy_(xB)
         if (tail is None) != (self.xtail is None):
             raise _lib.KsmiError("plan and call disagree about the shared tail channels (DEM)")
-        if tail is not None and tail.data_ptr() != self.xtail.data_ptr():
-            self.xtail.copy_(tail)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
-
-    def run_backward(self, dlogits=None):
-        if not self.with_backward:
-            raise _lib.KsmiError("plan was built without backward")
-        if dlogits is not None and dlogits.data_ptr() != self.dlogits.data_ptr():
-            self.dlogits.copy_(dlogits)
-        self.bwd.run()
+        return self._run_forward(self.logits, (xA, self.xA), (xB, self.xB), *([] if tail is None else [(tail, self.xtail)]))

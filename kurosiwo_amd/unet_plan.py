@@ -5,138 +5,75 @@ operand load; the consumer's input-gradient epilogue applies the ReLU mask and a
 pooling / upsampling / skip concatenation / the residual sum are materialised once.  Strided 3x3 and 1x1 convolutions get their
 input gradients as phase convolutions written through the strided output placement of the implicit-GEMM kernel.
 """
-import ctypes as C
-
 import os
 
 import torch
 
 from . import _lib
-from .changeformer_plan import BN_EPS, BN_MOMENTUM, CS, ChangeFormerPlan
-from .runtime import SrcSpec, conv_grid_m, conv_stats_rows, make_conv, make_wgrad
+from .conv_plan import BN_EPS, BN_MOMENTUM, CS, ConvPlan
+from .runtime import SrcSpec, conv_grid_m, make_conv, phase_taps_k3s2
 from .plan_base import _Saved
 from .unet import DECODER_CHANNELS, LAYERS
 
 
-class UnetPlan(ChangeFormerPlan):
-    slab_bias_side = False     # (measured on ChangeFormer only: plan_base._linear_wgrad)
-    input_names = ("x",)
-
-    side_tokens = False        # (ChangeFormerPlan's encoder switch: no MiT encoder here)
+class ResNetPlan(ConvPlan):
+    """torchvision ResNet-18 pieces shared by the Unet encoder and BIT-CD's siamese backbone: stem and BasicBlock"""
     side_wgrad = True          # plan_base.PlanBase.side_wgrad: dedicated buffers throughout (self.buf), conv weight gradients only
 
-    def __init__(self, model, B, H, W, dtype, training, with_backward):
-        self._init_base(model, dtype, with_backward)
-        self.B, self.H, self.W, self.training = B, H, W, training
-        self.cin, self.nc = model.in_channels, model.classes
-        self.x = torch.empty((B, self.cin, H, W), dtype=torch.float32, device=self.dev)
-        self.logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=self.dev)
-        self.dlogits = torch.empty_like(self.logits) if with_backward else None
-        self.const = torch.zeros((2, 512), dtype=torch.float32, device=self.dev)
-        self.const[1].fill_(1.0)
-        self._gbuf = {}            # id(tensor) -> gradient buffer ; first writer "=", later writers "+="
-        self._gacc = set()
-        self._bwd = []
-        self._build_unet()
-        if with_backward:
-            for f in reversed(self._bwd):
-                f()
-        self._finish()
-
-    # ---------------------------------------------------------------- gradient bookkeeping
-    def gbuf(self, t):
-        if id(t) not in self._gbuf:
-            self._gbuf[id(t)] = self.buf(*t.shape)
-        return self._gbuf[id(t)]
-
-    def gacc(self, t):
-        """accumulate flag for the next writer of d(t): 0 for the first one"""
-        a = 1 if id(t) in self._gacc else 0
-        self._gacc.add(id(t))
-        return a
-
-    # ---------------------------------------------------------------- building blocks
-    def _cv(self, ll, name, srcs, dsts, wkey, Hin, Win, Hout, Wout, k, stride, pad, N, Ktot, stats=False, mask=None, bias=None, tag="conv"):
-        d, table = make_conv(srcs, dsts, dsts[0][0], bias, None, self.B, Hin, Win, Hout, Wout, k, k, stride, pad, N, self.dtype, mask=mask)
-        taps = k * k
-        d.wpk = self._packed(wkey, table, taps, N, N, taps, Ktot * taps, 0, 1, 0).data_ptr()
-        rows = conv_stats_rows(d, self.dtype) if stats else conv_grid_m(d)   # (rows of the kernel that will run it: see changeformer_plan._conv3)
-        if stats:
-            self.need("stats", rows * 2 * d.Npad * 4)
-            self._later.append(lambda: setattr(d, "stats", self.scr("stats")))
-        self._conv(ll, d, f"{tag}{k}x{k}", name)
-        return rows, d.Npad
-
-    def _wg(self, srcs, dy, N, wkey, Hin, Win, Hout, Wout, k, stride, pad, Ktot):
-        taps = k * k
-        dw, ws = make_wgrad(srcs, dy, N, 0, N, self.m._g(wkey), taps, Ktot * taps, 1, self._acc_param(wkey), self.B, Hin, Win, Hout, Wout,
-                            k, k, stride, pad, self.dtype)
-        self._wgrad(dw, ws, wkey)
-
     def _dgrad_s2(self, name, dy, Cout, dx, Cin, H, W, wkey, acc):
-        """input gradient of a 3x3 stride-2 pad-1 convolution: dx[2m] = dy[m] W[1] ; dx[2m+1] = dy[m] W[2] + dy[m+1] W[0] per axis
-        -> four 2x2 phase convolutions over dy (a missing tap packs as zero) placed at (2m+py, 2n+px)"""
+        """input gradient of a 3x3 stride-2 pad-1 convolution: four 2x2 phase convolutions over dy (runtime.phase_taps_k3s2)"""
         Ho, Wo = H // 2, W // 2
         for py in range(2):
             for px in range(2):
-                tap_map = []
-                for a in range(2):
-                    for b in range(2):
-                        ky = (1 if a == 0 else -1) if py == 0 else (2 if a == 0 else 0)
-                        kx = (1 if b == 0 else -1) if px == 0 else (2 if b == 0 else 0)
-                        tap_map.append(-1 if ky < 0 or kx < 0 else ky * 3 + kx)
                 d, table = make_conv([SrcSpec(dy, Cout)], [(dx, Cin, 0, 0, Cin, acc)], dx, None, None, self.B, Ho, Wo, Ho, Wo, 2, 2, 1, 0, Cin,
                                      self.dtype, out_map=(2, 2, py, px, H, W))
-                d.wpk = self._packed(wkey, table, 4, Cin, Cin, Cin * 9, 9, 0, 1, 0, tap_map).data_ptr()
+                d.wpk = self._packed(wkey, table, 4, Cin, Cin, Cin * 9, 9, 0, 1, 0, phase_taps_k3s2(py, px)).data_ptr()
                 self._conv(self.bwd, d, "dgrad_s2_phase", f"{name}.p{py}{px}")
 
-    def _bnrelu_bwd(self, bnkey, dout, out, z, sv, dz, npix, Cc):
-        """out = relu(bn(z) [+ identity]) materialised: dout -> g (in place), dz, dgamma, dbeta"""
-        rows = max(1, min(512, npix // 256))
-        self.need("bnp", rows * 2 * Cc * 4)
-        self.need("bnsum", 2 * Cc * 4)
-        gw, gb = self.m._g(f"{bnkey}.weight").data_ptr(), self.m._g(f"{bnkey}.bias").data_ptr()
-        a1, _ = self._acc_param(f"{bnkey}.weight"), self._acc_param(f"{bnkey}.bias")
-        gamma = self.m._p(f"{bnkey}.weight").data_ptr()
-        dt = self.dt
-        self.bwd.add("ksmi_bnrelu_bwd_reduce", lambda: (dout.data_ptr(), out.data_ptr(), z.data_ptr(), sv.mean, sv.rstd, self.scr("bnp"), rows, npix, Cc, dt),
-                     self._elt_meta("bnrelu_bwd_reduce", 3 * npix * Cc))
-        # the partial rows finish inside the apply pass (bnfused.hip, as in the SNUNet plan since round 4): one launch less per BatchNorm;
-        # KSMI_BN_FUSED_FAMILIES=0 keeps the separate reduce_rows launch (A/B)
-        if os.environ.get("KSMI_BN_FUSED_FAMILIES", "1") != "0" and self.lib.ksmi_bn_fused_supported(Cc, Cc, dt):
-            self.bwd.add("ksmi_bnrelu_bwd_fin_apply", lambda: (self.scr("bnp"), rows, Cc, self.scr("bnsum"), gw, gb, a1, dout.data_ptr(), out.data_ptr(),
-                                                               z.data_ptr(), sv.mean, sv.rstd, gamma, dz.data_ptr(), float(npix), npix, Cc, dt),
-                         self._elt_meta("bnrelu_bwd_apply", 5 * npix * Cc))
-            self._mark(f"{bnkey}.weight", f"{bnkey}.bias")
-            return
-        self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("bnp"), rows, 2, Cc, Cc, self.scr("bnsum"), gw, gb, a1))
-        self._mark(f"{bnkey}.weight", f"{bnkey}.bias")
-        self.bwd.add("ksmi_bnrelu_bwd_apply", lambda: (dout.data_ptr(), out.data_ptr(), z.data_ptr(), sv.mean, sv.rstd, gamma, self.scr("bnsum"), dz.data_ptr(),
-                                                       float(npix), npix, Cc, dt), self._elt_meta("bnrelu_bwd_apply", 5 * npix * Cc))
+    # ---------------------------------------------------------------- conv1 7x7 s2 -> bn1 -> relu -> maxpool 3x3 s2
+    def _resnet_stem(self, prefix, x):
+        """x: fp32 NCHW input tile -> (stem output before the pool, pooled output, its height, width)"""
+        B, H, W, dt = self.B, self.H, self.W, self.dt
+        H1, W1 = H // 2, W // 2
+        R1 = B * H1 * W1
+        kc = 32 if self.dtype == torch.bfloat16 else 16
+        Kreal = self.cin * 49
+        Kpad = -(-Kreal // kc) * kc
+        col, s0, f1 = self.buf(R1, Kpad), self.buf(R1, 64), self.buf(B, H1, W1, 64)
+        sv0 = _Saved(64, self.dev)
+        self.fwd.add("ksmi_im2col", lambda: (x.data_ptr(), col.data_ptr(), B, self.cin, H, W, H1, W1, 7, 7, 2, 3, Kpad, 1, dt),
+                     self._elt_meta("im2col", 2 * R1 * Kpad))
+        d, table = make_conv([SrcSpec(col, Kpad, k_real=Kreal)], [(s0, 64, 0, 0, 64, 0)], s0, None, None, 1, R1, 1, R1, 1, 1, 1, 1, 0, 64, self.dtype)
+        d.wpk = self._packed(f"{prefix}.conv1.weight", table, 1, 64, 64, 1, Kreal, 0, 0).data_ptr()
+        rows0 = self._attach_stats(d) if self.training else conv_grid_m(d)
+        self._conv(self.fwd, d, "stem7x7", f"{prefix}.conv1")
+        self._bn_finalize(f"{prefix}.bn1", sv0, rows0, d.Npad, 64, R1)
+        self._affine(self.fwd, s0, sv0, f1, R1, 64, 1)
+        H2, W2 = H1 // 2, W1 // 2
+        p = self.buf(B, H2, W2, 64)
+        # with a backward pass the forward records the window position of each first maximum (one byte per output element): the backward
+        # compares codes instead of re-reading up to four windows per input element (325 -> ~40 us at 112 x 112 x 64 x 32 images)
+        pidx = torch.empty(p.numel(), dtype=torch.uint8, device=self.dev) if self.with_backward and not os.environ.get("KSMI_MAXPOOL_GATHER") else None
+        if pidx is not None:
+            self.fwd.add("ksmi_maxpool3x3s2_forward_idx", lambda: (f1.data_ptr(), p.data_ptr(), pidx.data_ptr(), B, H1, W1, 64, dt),
+                         self._elt_meta("maxpool3", 2 * R1 * 64))
+        else:
+            self.fwd.add("ksmi_maxpool3x3s2_forward", lambda: (f1.data_ptr(), p.data_ptr(), B, H1, W1, 64, dt), self._elt_meta("maxpool3", 2 * R1 * 64))
 
-    def _bn_plain_bwd(self, bnkey, dy, x, sv, dv, npix, Cc):
-        rows = max(1, min(512, npix // 256))
-        self.need("bnp", rows * 2 * Cc * 4)
-        self.need("bnsum", 2 * Cc * 4)
-        gw, gb = self.m._g(f"{bnkey}.weight").data_ptr(), self.m._g(f"{bnkey}.bias").data_ptr()
-        a1, _ = self._acc_param(f"{bnkey}.weight"), self._acc_param(f"{bnkey}.bias")
-        gamma = self.m._p(f"{bnkey}.weight").data_ptr()
-        dt = self.dt
-        self.bwd.add("ksmi_bn_bwd_reduce", lambda: (dy.data_ptr(), x.data_ptr(), sv.mean, sv.rstd, self.scr("bnp"), rows, npix, Cc, dt),
-                     self._elt_meta("bn_bwd_reduce", 2 * npix * Cc))
-        self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("bnp"), rows, 2, Cc, Cc, self.scr("bnsum"), gw, gb, a1))
-        self._mark(f"{bnkey}.weight", f"{bnkey}.bias")
-        self.bwd.add("ksmi_bn_bwd_apply", lambda: (dy.data_ptr(), x.data_ptr(), sv.mean, sv.rstd, gamma, self.scr("bnsum"), dv.data_ptr(), 0, float(npix),
-                                                   npix, Cc, dt), self._elt_meta("bn_bwd_apply", 3 * npix * Cc))
-
-    def _bnmask(self, z, sv):
-        """epilogue mask of a consumer's input gradient: ReLU(bn(z)) active set + BatchNorm-backward sums"""
-        return (z, sv.t[0], sv.t[1], sv.t[2], sv.t[3])
-
-    def _affine(self, ll, x, sv, y, npix, Cc, relu):
-        dt = self.dt
-        ll.add("ksmi_affine", lambda: (x.data_ptr(), sv.scale, sv.shift, y.data_ptr(), npix, Cc, relu, C.c_float(1.0), dt),
-               self._elt_meta("bn_apply", 2 * npix * Cc))
+        def bwd():
+            df1, ds0 = self.gbuf(f1), self.buf(R1, 64)
+            dp = self.gbuf(p)
+            acc = self.gacc(f1)
+            if pidx is not None:
+                self.bwd.add("ksmi_maxpool3x3s2_backward_idx", lambda: (pidx.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
+                             self._elt_meta("maxpool3_bwd", 2 * R1 * 64 + R1 * 64 // 2 + R1 * 64 // 4))
+            else:
+                self.bwd.add("ksmi_maxpool3x3s2_backward", lambda: (f1.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
+                             self._elt_meta("maxpool3_bwd", 4 * R1 * 64))
+            self._bnrelu_bwd(f"{prefix}.bn1", df1, f1, s0, sv0, ds0, R1, 64)
+            self._linear_bwd(f"{prefix}.conv1", col, Kpad, f"{prefix}.conv1.weight", None, ds0, 64, R1, None, k_real=Kreal)
+        self._bwd.append(bwd)
+        return f1, p, H2, W2
 
     # ---------------------------------------------------------------- BasicBlock (torchvision resnet.py)
     def _basic_block(self, k, x_in, Cin, Cout, H, W, stride):
@@ -155,7 +92,7 @@ class UnetPlan(ChangeFormerPlan):
         # bn2: its statistics finish inside the apply pass below when that is available (bnfused.hip: one launch instead of two; the
         # downsample branch in between writes other rows of the shared statistics scratch, so it needs its own finalize first)
         down = f"{k}.downsample.0.weight" in self.m._pspec
-        fuse2 = (self.training and not down and os.environ.get("KSMI_BN_FUSED_FAMILIES", "1") != "0"
+        fuse2 = (self.training and not down and self._bn_fused
                  and bool(self.lib.ksmi_bn_fused_supported(Cout, cpad2, dt)))
         if not fuse2:
             self._bn_finalize(f"{k}.bn2", sv2, rows, cpad, Cout, npix)
@@ -212,6 +149,18 @@ class UnetPlan(ChangeFormerPlan):
         self._bwd.append(bwd)
         return out
 
+
+class UnetPlan(ResNetPlan):
+    input_names = ("x",)
+
+    def __init__(self, model, B, H, W, dtype, training, with_backward):
+        self._init_conv(model, B, H, W, dtype, training, with_backward)
+        self.cin, self.nc = model.in_channels, model.classes
+        self.x = torch.empty((B, self.cin, H, W), dtype=torch.float32, device=self.dev)
+        self.logits = torch.empty((B, self.nc, H, W), dtype=torch.float32, device=self.dev)
+        self.dlogits = torch.empty_like(self.logits) if with_backward else None
+        self._build_lists(self._build_unet)
+
     # ---------------------------------------------------------------- DecoderBlock (smp unet/decoder.py)
     def _decoder_block(self, k, xd, Cin, skip, Cs, Cout, h, w):
         B, dt = self.B, self.dt
@@ -252,49 +201,8 @@ class UnetPlan(ChangeFormerPlan):
 
     # ---------------------------------------------------------------- the graph
     def _build_unet(self):
-        m, B, H, W, dt = self.m, self.B, self.H, self.W, self.dt
-        H1, W1 = H // 2, W // 2
-        R1 = B * H1 * W1
-        kc = 32 if self.dtype == torch.bfloat16 else 16
-        Kreal = self.cin * 49
-        Kpad = -(-Kreal // kc) * kc
-        col, s0, f1 = self.buf(R1, Kpad), self.buf(R1, 64), self.buf(B, H1, W1, 64)
-        sv0 = _Saved(64, self.dev)
-        self.fwd.add("ksmi_im2col", lambda: (self.x.data_ptr(), col.data_ptr(), B, self.cin, H, W, H1, W1, 7, 7, 2, 3, Kpad, 1, dt), self._elt_meta("im2col", 2 * R1 * Kpad))
-        d, table = make_conv([SrcSpec(col, Kpad, k_real=Kreal)], [(s0, 64, 0, 0, 64, 0)], s0, None, None, 1, R1, 1, R1, 1, 1, 1, 1, 0, 64, self.dtype)
-        d.wpk = self._packed("encoder.conv1.weight", table, 1, 64, 64, 1, Kreal, 0, 0).data_ptr()
-        rows0 = conv_stats_rows(d, self.dtype) if self.training else conv_grid_m(d)   # (rows of the kernel that will run it: see changeformer_plan._conv3)
-        if self.training:
-            self.need("stats", rows0 * 2 * d.Npad * 4)
-            self._later.append(lambda: setattr(d, "stats", self.scr("stats")))
-        self._conv(self.fwd, d, "stem7x7", "encoder.conv1")
-        self._bn_finalize("encoder.bn1", sv0, rows0, d.Npad, 64, R1)
-        self._affine(self.fwd, s0, sv0, f1, R1, 64, 1)
-        H2, W2 = H1 // 2, W1 // 2
-        p = self.buf(B, H2, W2, 64)
-        # with a backward pass the forward records the window position of each first maximum (one byte per output element): the backward
-        # compares codes instead of re-reading up to four windows per input element (325 -> ~40 us at 112 x 112 x 64 x 32 images)
-        pidx = torch.empty(p.numel(), dtype=torch.uint8, device=self.dev) if self.with_backward and not os.environ.get("KSMI_MAXPOOL_GATHER") else None
-        if pidx is not None:
-            self.fwd.add("ksmi_maxpool3x3s2_forward_idx", lambda: (f1.data_ptr(), p.data_ptr(), pidx.data_ptr(), B, H1, W1, 64, dt),
-                         self._elt_meta("maxpool3", 2 * R1 * 64))
-        else:
-            self.fwd.add("ksmi_maxpool3x3s2_forward", lambda: (f1.data_ptr(), p.data_ptr(), B, H1, W1, 64, dt), self._elt_meta("maxpool3", 2 * R1 * 64))
-
-        def stem_bwd():
-            df1, ds0 = self.gbuf(f1), self.buf(R1, 64)
-            dp = self.gbuf(p)
-            acc = self.gacc(f1)
-            if pidx is not None:
-                self.bwd.add("ksmi_maxpool3x3s2_backward_idx", lambda: (pidx.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
-                             self._elt_meta("maxpool3_bwd", 2 * R1 * 64 + R1 * 64 // 2 + R1 * 64 // 4))
-            else:
-                self.bwd.add("ksmi_maxpool3x3s2_backward", lambda: (f1.data_ptr(), dp.data_ptr(), df1.data_ptr(), acc, B, H1, W1, 64, dt),
-                             self._elt_meta("maxpool3_bwd", 4 * R1 * 64))
-            self._bnrelu_bwd("encoder.bn1", df1, f1, s0, sv0, ds0, R1, 64)
-            self._linear_bwd("encoder.conv1", col, Kpad, "encoder.conv1.weight", None, ds0, 64, R1, None, k_real=Kreal)
-        self._bwd.append(stem_bwd)
-
+        B, H, W, dt = self.B, self.H, self.W, self.dt
+        f1, p, H2, W2 = self._resnet_stem("encoder", self.x)
         feats = [f1]
         t, cin, h, w = p, 64, H2, W2
         for li, (ch, stride) in enumerate(LAYERS):
@@ -317,35 +225,11 @@ class UnetPlan(ChangeFormerPlan):
         P = self.buf(B, H, W, CS)
         nc = self.nc
         self._cv(self.fwd, "segmentation_head", [SrcSpec(y, 16)], [(P, CS, 0, 0, nc, 0)], "segmentation_head.0.weight", H, W, H, W, 3, 1, 1, nc, 16,
-                 bias=m._p("segmentation_head.0.bias"))
+                 bkey="segmentation_head.0.bias")
         HW = H * W
         self.fwd.add("ksmi_out_to_nchw", lambda: (P.data_ptr(), self.logits.data_ptr(), B, nc, CS, HW, 0, dt))
-
-        def head_bwd():
-            dP = self.buf(B * HW, CS)
-            dy = self.gbuf(y)
-            self.gacc(y)
-            wk, bk = "segmentation_head.0.weight", "segmentation_head.0.bias"
-            self.bwd.add("ksmi_dout_to_nhwc", lambda: (self.dlogits.data_ptr(), self.logits.data_ptr(), dP.data_ptr(), B, nc, CS, HW, 0, dt))
-            psrc = [SrcSpec(dP, CS, 0, CS, k_real=nc)]
-            self._conv3(self.bwd, "segmentation_head", psrc, [(dy, 16, 0, 0, 16, 0)], wk, None, B, H, W, 16, nc, dgrad=True)
-            gview = m._g(wk)[8:]
-            self.keep.append(gview)
-            dw, ws = make_wgrad(psrc, y, 16, 0, 16, gview, 16 * 9, 9, -1, self._acc_param(wk), B, H, W, H, W, 3, 3, 1, 1, self.dtype)
-            self._wgrad(dw, ws, wk)
-            rr = max(1, min(512, B * HW // 256))
-            self.need("red", rr * CS * 4)
-            accb = self._acc_param(bk)
-            gb = m._g(bk).data_ptr()
-            self.bwd.add("ksmi_channel_sum", lambda: (dP.data_ptr(), self.scr("red"), rr, B * HW, CS, dt), self._elt_meta("channel_sum", B * HW * CS))
-            self.bwd.add("ksmi_reduce_rows", lambda: (self.scr("red"), rr, 1, CS, nc, None, None, gb, accb))
-            self._mark(bk)
-        self._bwd.append(head_bwd)
+        self._bwd.append(lambda: self._class_head_bwd("segmentation_head", "segmentation_head.0.weight", "segmentation_head.0.bias", y, 16))
 
     # ---------------------------------------------------------------- execution
     def run_forward(self, x):
-        if x.data_ptr() != self.x.data_ptr():
-            self.x.copy_(x)
-        self.packs.run()
-        self.fwd.run()
-        return self.logits
+        return self._run_forward(self.logits, (x, self.x))

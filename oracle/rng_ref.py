@@ -40,7 +40,7 @@ def draws(seed, step, site, first, count):
 
 
 def threshold(p):
-    """(thr, inv_keep) exactly as kurosiwo_amd/changeformer_plan.py:drop_threshold"""
+    """(thr, inv_keep) exactly as kurosiwo_amd/conv_plan.py:drop_threshold"""
     if p <= 0.0:
         return 0, 1.0
     return min(0xFFFFFFFF, int(round(p * 4294967296.0))), 1.0 / (1.0 - p)

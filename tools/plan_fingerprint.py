@@ -4,7 +4,7 @@ run it on two commits in the same environment and compare the outputs (byte-iden
 
   python tools/plan_fingerprint.py [--device cpu] [--families snunet,mae,...] > plans.txt ; sha256sum plans.txt
 
-Per plan (seven families, constructors as in bench.py; train and eval, bf16 and fp32, 224 x 224, a small batch so that the
+Per plan (every family, constructors as in bench.py; FC-Siam-diff and the other three BIT-CD networks under names of their own; train and eval, bf16 and fp32, 224 x 224, a small batch so that the
 convolutional plans fit in host memory; SNUNet also with base_channel 16 at 32 x 32, with tail=1 and with sync_bn) and per list
 (packs, fwd, bwd) one line per entry: index, entry name, meta (every key; callables by their presence) and the resolved arguments.
 Scalars are literal.  A descriptor passed by reference (ConvDesc, WgradDesc, ...) and the pack / row-sum descriptor tables are
@@ -121,6 +121,13 @@ def models(family, precision):
         from kurosiwo_amd.bitcd import define_G
         yield ("bit-cd base_transformer_pos_s4_dd8 B2", define_G({"net_G": "base_transformer_pos_s4_dd8"}, 2, precision=precision),
                (2, H, W, True, True), (2, H, W, False, False))
+    elif family == "siam-diff":
+        from kurosiwo_amd.fcsiam import SiamUnet_diff
+        yield "siam-diff B2", SiamUnet_diff(2, 3, precision=precision), (2, H, W, True, True), (2, H, W, False, False)
+    elif family == "bit-cd-variants":
+        from kurosiwo_amd.bitcd import define_G
+        for net_g in ("base_resnet18", "base_transformer_pos_s4", "base_transformer_pos_s4_dd8_dedim8"):
+            yield f"bit-cd {net_g} B2", define_G({"net_G": net_g}, 2, precision=precision), (2, H, W, True, True), (2, H, W, False, False)
     elif family == "floodvit":
         from kurosiwo_amd.floodvit import FinetunerSegmentation, ViT
         enc = ViT(image_size=224, patch_size=16, num_classes=1000, dim=1024, depth=24, heads=16, mlp_dim=2048, channels=6)
@@ -134,7 +141,8 @@ def models(family, precision):
         raise SystemExit(f"unknown family {family}")
 
 
-FAMILIES = ("snunet", "changeformer", "unet", "siam-conc", "bit-cd", "floodvit", "mae")
+# (new families are appended: the dump of the earlier names, and its hash in LABNOTES, stays comparable across commits)
+FAMILIES = ("snunet", "changeformer", "unet", "siam-conc", "bit-cd", "floodvit", "mae", "siam-diff", "bit-cd-variants")
 
 
 def main():
