@@ -1,7 +1,8 @@
 """Flat-arena nn.Module base: every parameter is a view into ONE fp32 buffer (gradients into a
 second one), registered under the reference's state-dict key names.  The optimiser step and the
 data-parallel all-reduce are then single flat operations, and a model plan can hand raw device
-pointers to the C-ABI.  (SNUNet_ECAM predates this class and carries its own copy with buffers.)
+pointers to the C-ABI.  Every model class derives from ArenaModule: it builds its key -> shape specs, calls `_setup_arena`,
+initialises the views, and its `plan()` / `forward()` go through `_cached_plan` / `_apply_plan`.
 """
 from collections import OrderedDict
 
@@ -27,16 +28,31 @@ def _as_i32(words):
     return torch.tensor([v - (1 << 32) if v >= (1 << 31) else v for v in words], dtype=torch.int32)
 
 
+def bn_spec(p, b, c, name, ch):
+    """one BatchNorm2d in the (params, fp32 buffers, int64 counters) specs of a model"""
+    p[f"{name}.weight"] = (ch,)
+    p[f"{name}.bias"] = (ch,)
+    b[f"{name}.running_mean"] = (ch,)
+    b[f"{name}.running_var"] = (ch,)
+    c[f"{name}.num_batches_tracked"] = ()
+
+
 class ArenaModule(nn.Module):
+    ARENA_ALIGN = 8            # parameter views, in floats: 32-byte aligned views (16-byte aligned rows in the bf16 mirror)
+
     def _setup_arena(self, pspec, bspec=None, ispec=None):
         """pspec: OrderedDict key -> shape, in the reference's registration order; bspec: fp32 buffers (BatchNorm running
-        statistics); ispec: int64 counters (num_batches_tracked)."""
+        statistics: every key ends in running_mean or running_var); ispec: int64 counters (num_batches_tracked).  The arenas
+        start at zero, so only running_var needs its BatchNorm default of 1."""
         self._pspec = OrderedDict(pspec)
         self._bspec = OrderedDict(bspec or {})
         self._ispec = OrderedDict(ispec or {})
         self._plans = {}
         self._anchor = None
         self._build_arenas(torch.device("cpu"))
+        for key in self._bspec:
+            if key.endswith("running_var"):
+                self._b(key).fill_(1.0)
 
     def _holder(self, path):
         mod = self
@@ -50,7 +66,7 @@ class ArenaModule(nn.Module):
         offs, o = OrderedDict(), 0
         for k, shp in self._pspec.items():
             offs[k] = o
-            o += -(-max(_numel(shp), 1) // 8) * 8            # 32-byte aligned views (16-byte aligned rows in the bf16 mirror)
+            o += -(-max(_numel(shp), 1) // self.ARENA_ALIGN) * self.ARENA_ALIGN
         self._poff = offs
         self.flat_params = torch.zeros(o, dtype=torch.float32, device=device)
         self.flat_grads = torch.zeros(o, dtype=torch.float32, device=device)
@@ -165,6 +181,28 @@ class ArenaModule(nn.Module):
             if p.requires_grad:
                 p.grad = self._g(key).view(shp)
 
+    # ---- the one path from a model's forward() to its plan
+    def _cached_plan(self, key, build):
+        """the plan of `key`, built by build() on first use (a rebuilt arena empties the cache: plans hold raw pointers)"""
+        self._ensure_arena()
+        if key not in self._plans:
+            self._plans[key] = build()
+        return self._plans[key]
+
+    def _wants_grad(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _grad_anchor(self, device):
+        """dummy leaf that makes autograd call the whole-model node"""
+        if self._anchor is None or self._anchor.device != device:
+            self._anchor = torch.zeros(1, device=device, requires_grad=True)
+        return self._anchor
+
+    def _apply_plan(self, plan, want_grad, *inputs):
+        if not want_grad:
+            return plan.run_forward(*inputs).clone()
+        return PlanFn.apply(self._grad_anchor(inputs[0].device), self, plan, *inputs)
+
     def _check_no_grads(self):
         if any(p.grad is not None for p in self.parameters()):
             raise _lib.KsmiError("gradient accumulation across backward() calls is not supported by the HIP plan: "
@@ -190,7 +228,7 @@ class PlanFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, model, plan, *inputs):
-        ctx.model, ctx.plan = model, plan
+        ctx.model, ctx.plan, ctx.n_inputs = model, plan, len(inputs)
         ctx.gen = stamp_forward(plan)
         return plan.run_forward(*inputs).clone()
 
@@ -201,4 +239,4 @@ class PlanFn(torch.autograd.Function):
         model._check_no_grads()
         plan.run_backward(dout.contiguous().float())
         model._attach_grads()
-        return (None,) * (3 + len(plan.input_names))
+        return (None,) * (3 + ctx.n_inputs)

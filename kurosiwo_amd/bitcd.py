@@ -11,12 +11,13 @@ backbone: they receive no gradient; the fused optimizer still applies its weight
 for `grad is None` -- no effect on any output), train / eval BatchNorm semantics with the shared backbone normalising each date on
 its own.  Runs on the ResNet / decoder kernels of the U1 row (kurosiwo_amd/unet_plan.py).
 """
+import functools
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
-from .arena import ArenaModule, PlanFn
+from .arena import ArenaModule, bn_spec
 from .runtime import require_gpu
 
 LAYERS = ((64, 1), (128, 2), (256, 1), (512, 1))      # (planes, stride of the first block): layer3/4 "dilated" = stride 1
@@ -24,13 +25,7 @@ LAYERS = ((64, 1), (128, 2), (256, 1), (512, 1))      # (planes, stride of the f
 
 def bitcd_specs(input_nc, output_nc):
     p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
-
-    def bn(name, ch):
-        p[f"{name}.weight"] = (ch,)
-        p[f"{name}.bias"] = (ch,)
-        b[f"{name}.running_mean"] = (ch,)
-        b[f"{name}.running_var"] = (ch,)
-        c[f"{name}.num_batches_tracked"] = ()
+    bn = functools.partial(bn_spec, p, b, c)
     p["resnet.conv1.weight"] = (64, input_nc, 7, 7)
     bn("resnet.bn1", 64)
     cin = 64
@@ -78,29 +73,21 @@ class ResNet(ArenaModule):
                     v.normal_(1.0, init_gain)
                 else:
                     v.normal_(0.0, init_gain)
-            for key in self._bspec:
-                self._b(key).fill_(1.0 if key.endswith("running_var") else 0.0)
 
     def plan(self, B, H, W, training, with_backward):
-        self._ensure_arena()
-        key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward))
-        if key not in self._plans:
+        def build():
             from .bitcd_plan import BitCDPlan
-            self._plans[key] = BitCDPlan(self, B, H, W, self.act_dtype(), training, with_backward)
-        return self._plans[key]
+            return BitCDPlan(self, B, H, W, self.act_dtype(), training, with_backward)
+        return self._cached_plan((B, H, W, self.act_dtype(), bool(training), bool(with_backward)), build)
 
     def forward(self, x1, x2):
         require_gpu(x1)
         if x1.shape != x2.shape or x1.dim() != 4 or x1.shape[1] != self.input_nc or x1.shape[2] % 32 or x1.shape[3] % 32:
             raise ValueError(f"expected two [B,{self.input_nc},H,W] tensors with H, W multiples of 32, got {tuple(x1.shape)} {tuple(x2.shape)}")
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(x1.shape[0], x1.shape[2], x1.shape[3], self.training, want_grad)
         x1, x2 = x1.contiguous().float(), x2.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(x1, x2).clone()
-        if self._anchor is None or self._anchor.device != x1.device:
-            self._anchor = torch.zeros(1, device=x1.device, requires_grad=True)
-        return PlanFn.apply(self._anchor, self, plan, x1, x2)
+        return self._apply_plan(plan, want_grad, x1, x2)
 
 
 def transformer_specs(input_nc, output_nc, token_len, enc_depth, dec_depth, dim_head, decoder_dim_head, with_pos):
@@ -169,16 +156,12 @@ class BASE_Transformer(ResNet):
                     v.normal_(1.0, init_gain)
                 else:
                     v.normal_(0.0, init_gain)
-            for key in self._bspec:
-                self._b(key).fill_(1.0 if key.endswith("running_var") else 0.0)
 
     def plan(self, B, H, W, training, with_backward):
-        self._ensure_arena()
-        key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward))
-        if key not in self._plans:
+        def build():
             from .bitcd_plan import BitCDTransformerPlan
-            self._plans[key] = BitCDTransformerPlan(self, B, H, W, self.act_dtype(), training, with_backward)
-        return self._plans[key]
+            return BitCDTransformerPlan(self, B, H, W, self.act_dtype(), training, with_backward)
+        return self._cached_plan((B, H, W, self.act_dtype(), bool(training), bool(with_backward)), build)
 
 
 def define_G(args, in_channels, precision="bf16"):

@@ -17,8 +17,6 @@ from .unet_plan import ResNetPlan
 
 
 class BitCDPlan(ResNetPlan):
-    input_names = ("x1", "x2")
-
     def __init__(self, model, B, H, W, dtype, training, with_backward):
         self._init_conv(model, B, H, W, dtype, training, with_backward)
         self.cin, self.nc = model.input_nc, model.output_nc

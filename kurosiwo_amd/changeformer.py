@@ -19,13 +19,14 @@ reference's own modules run with their Dropout / DropPath draws replaced by that
 Only the gradient of the last output (`cp`) is propagated: the reference trainer's default `multi_scale_train: false`
 (configs/method/changeformer/changeformer.json, change_detection_trainer.py:138-166).
 """
+import functools
 import math
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
-from .arena import ArenaModule, _numel
+from .arena import ArenaModule, _numel, bn_spec, check_forward_stamp, stamp_forward
 from .runtime import require_gpu
 
 EMBED_DIMS = (64, 128, 320, 512)
@@ -37,13 +38,7 @@ SR_RATIOS = (8, 4, 2, 1)
 def changeformer_specs(input_nc, output_nc, embed_dim):
     """(params, fp32 buffers, int64 counters) keyed and ordered as the reference's state dict."""
     p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
-
-    def bn(name, ch):
-        p[f"{name}.weight"] = (ch,)
-        p[f"{name}.bias"] = (ch,)
-        b[f"{name}.running_mean"] = (ch,)
-        b[f"{name}.running_var"] = (ch,)
-        c[f"{name}.num_batches_tracked"] = ()
+    bn = functools.partial(bn_spec, p, b, c)
     cin = input_nc
     for i, ch in enumerate(EMBED_DIMS):
         k = f"Tenc_x2.patch_embed{i + 1}"
@@ -150,41 +145,36 @@ class ChangeFormerV6(ArenaModule):
                 else:
                     fan_in = shp[0] * shp[2] * shp[3] if (len(shp) == 4 and "convd" in key) else _numel(shp[1:])
                     p.uniform_(-1 / math.sqrt(fan_in), 1 / math.sqrt(fan_in))
-            for key in self._bspec:
-                self._b(key).fill_(1.0 if key.endswith("running_var") else 0.0)
 
     def _is_bn(self, key):
         return (key.rsplit(".", 1)[0] + ".running_mean") in self._bspec
 
     def plan(self, B, H, W, training, with_backward):
-        self._ensure_arena()
         key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward),
                (self.drop_rate, self.attn_drop, self.drop_path_rate) if training else None)
-        if key not in self._plans:
+
+        def build():
             from .changeformer_plan import ChangeFormerPlan
-            self._plans[key] = ChangeFormerPlan(self, B, H, W, self.act_dtype(), training, with_backward)
-        return self._plans[key]
+            return ChangeFormerPlan(self, B, H, W, self.act_dtype(), training, with_backward)
+        return self._cached_plan(key, build)
 
     def forward(self, x1, x2):
         require_gpu(x1)
         if x1.shape != x2.shape or x1.dim() != 4 or x1.shape[1] != self.input_nc:
             raise ValueError(f"expected two [B,{self.input_nc},H,W] tensors, got {tuple(x1.shape)} {tuple(x2.shape)}")
         B, _, H, W = x1.shape
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(B, H, W, self.training, want_grad)
         x1, x2 = x1.contiguous().float(), x2.contiguous().float()
         if not want_grad:
             plan.run_forward(x1, x2)
             return [o.clone() for o in plan.outputs]
-        if self._anchor is None or self._anchor.device != x1.device:
-            self._anchor = torch.zeros(1, device=x1.device, requires_grad=True)
-        return list(_ChangeFormerFn.apply(self._anchor, x1, x2, self, plan))
+        return list(_ChangeFormerFn.apply(self._grad_anchor(x1.device), x1, x2, self, plan))
 
 
 class _ChangeFormerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, x1, x2, model, plan):
-        from .arena import stamp_forward
         ctx.model, ctx.plan = model, plan
         ctx.gen = stamp_forward(plan)
         ctx.set_materialize_grads(False)
@@ -198,7 +188,6 @@ class _ChangeFormerFn(torch.autograd.Function):
             raise NotImplementedError("ChangeFormerV6 (HIP): only the last output (cp) is differentiable (multi_scale_train = false)")
         if douts[-1] is None:
             return (None,) * 5
-        from .arena import check_forward_stamp
         check_forward_stamp(plan, ctx.gen)
         model._check_no_grads()
         plan.run_backward(douts[-1].contiguous().float())

@@ -23,7 +23,6 @@ NO_SITE = (0, 1.0, 0)
 
 
 class ChangeFormerPlan(ConvPlan):
-    input_names = ("x1", "x2")
     # the encoder's nn.Linear / sr-conv weight gradients on the train step's side stream (plan_base.PlanBase.side_tokens; waits in
     # _encoder_stage_bwd).  KSMI_CF_SIDE_TOKENS=0: the single-stream list.
     side_tokens = os.environ.get("KSMI_CF_SIDE_TOKENS", "1") != "0"

@@ -12,13 +12,14 @@ weight / input gradients run on the implicit-GEMM MFMA kernels with the concat o
 BN-apply + ReLU + Dropout2d is one elementwise kernel whose (sample, channel) mask comes from the counter-based stream
 (csrc/common.h) and is read back from `out > 0` in the backward pass.
 """
+import functools
 import math
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
-from .arena import ArenaModule, PlanFn
+from .arena import ArenaModule, bn_spec
 from .runtime import require_gpu
 
 # encoder: (name, Cout) per stage; decoder: per stage the upconv channel count and the (name, Cout) chain (siam_conc.py:19-93)
@@ -30,13 +31,7 @@ DROP2D = 0.2
 
 def fcsiam_specs(input_nbr, label_nbr, diff):
     p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
-
-    def bn(name, ch):
-        p[f"{name}.weight"] = (ch,)
-        p[f"{name}.bias"] = (ch,)
-        b[f"{name}.running_mean"] = (ch,)
-        b[f"{name}.running_var"] = (ch,)
-        c[f"{name}.num_batches_tracked"] = ()
+    bn = functools.partial(bn_spec, p, b, c)
     cin = input_nbr
     for stage in ENCODER:
         for name, co in stage:
@@ -78,29 +73,21 @@ class _SiamUnet(ArenaModule):
                 w = shp if len(shp) == 4 else self._pspec[key[:-4] + "weight"]
                 fan_in = w[1] * 9            # torch takes weight.size(1) * k*k for Conv2d and ConvTranspose2d alike
                 v.uniform_(-1 / math.sqrt(fan_in), 1 / math.sqrt(fan_in))
-            for key in self._bspec:
-                self._b(key).fill_(1.0 if key.endswith("running_var") else 0.0)
 
     def plan(self, B, H, W, training, with_backward):
-        self._ensure_arena()
-        key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward), self.drop2d if training else None)
-        if key not in self._plans:
+        def build():
             from .fcsiam_plan import FCSiamPlan
-            self._plans[key] = FCSiamPlan(self, B, H, W, self.act_dtype(), training, with_backward)
-        return self._plans[key]
+            return FCSiamPlan(self, B, H, W, self.act_dtype(), training, with_backward)
+        return self._cached_plan((B, H, W, self.act_dtype(), bool(training), bool(with_backward), self.drop2d if training else None), build)
 
     def forward(self, x1, x2):
         require_gpu(x1)
         if x1.shape != x2.shape or x1.dim() != 4 or x1.shape[1] != self.input_nbr or x1.shape[2] % 16 or x1.shape[3] % 16:
             raise ValueError(f"expected two [B,{self.input_nbr},H,W] tensors with H, W multiples of 16, got {tuple(x1.shape)} {tuple(x2.shape)}")
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(x1.shape[0], x1.shape[2], x1.shape[3], self.training, want_grad)
         x1, x2 = x1.contiguous().float(), x2.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(x1, x2).clone()
-        if self._anchor is None or self._anchor.device != x1.device:
-            self._anchor = torch.zeros(1, device=x1.device, requires_grad=True)
-        return PlanFn.apply(self._anchor, self, plan, x1, x2)
+        return self._apply_plan(plan, want_grad, x1, x2)
 
 
 class SiamUnet_conc(_SiamUnet):

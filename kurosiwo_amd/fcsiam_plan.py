@@ -25,8 +25,6 @@ LAYERS = [n for st in ENCODER for n, _ in st] + [n for _, _, ch in DECODER for n
 
 
 class FCSiamPlan(ConvPlan):
-    input_names = ("x1", "x2")
-
     side_wgrad = False         # measured: many short launches, the fork events cost more than the overlap returns (4346 -> 4214 tiles/s)
 
     def __init__(self, model, B, H, W, dtype, training, with_backward):

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .arena import ArenaModule, PlanFn, _numel
+from .arena import ArenaModule, _numel
 from .runtime import require_gpu
 
 
@@ -194,28 +194,24 @@ class FinetunerSegmentation(ArenaModule):
                     self._param_obj(key).requires_grad_(False)
 
     def plan(self, B, training, with_backward):
-        self._ensure_arena()
         # the plan skips the encoder's backward when every encoder parameter is frozen (linear_eval): part of the key
         enc_trains = any(self._param_obj(k).requires_grad for k in self._pspec if k.startswith("model."))
         key = (B, self.act_dtype(), bool(training), bool(with_backward), enc_trains)
-        if key not in self._plans:
+
+        def build():
             from .floodvit_plan import FloodViTPlan
-            self._plans[key] = FloodViTPlan(self, B, self.act_dtype(), with_backward)
-        return self._plans[key]
+            return FloodViTPlan(self, B, self.act_dtype(), with_backward)
+        return self._cached_plan(key, build)
 
     def forward(self, x):
         require_gpu(x)
         ih, iw = self.hp["image_size"]
         if x.dim() != 4 or tuple(x.shape[1:]) != (self.hp["channels"], ih, iw):
             raise ValueError(f"expected [B,{self.hp['channels']},{ih},{iw}], got {tuple(x.shape)}")
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(x.shape[0], self.training, want_grad)
         x = x.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(x).clone()
-        if self._anchor is None or self._anchor.device != x.device:
-            self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-        return PlanFn.apply(self._anchor, self, plan, x)
+        return self._apply_plan(plan, want_grad, x)
 
 
 def num_params(spec):

@@ -21,7 +21,6 @@ from .runtime import SrcSpec, make_conv, make_wgrad
 class FloodViTPlan(PlanBase):
     # the nn.Linear weight gradients of the transformer layers on the train step's side stream (plan_base.PlanBase.side_tokens)
     side_tokens = os.environ.get("KSMI_SIDE_TOKENS", "1") != "0"
-    input_names = ("x",)
 
     def __init__(self, model, B, dtype, with_backward):
         self._init_base(model, dtype, with_backward)

@@ -21,7 +21,7 @@ from collections import OrderedDict
 import torch
 
 from . import _lib
-from .arena import ArenaModule, PlanFn
+from .arena import ArenaModule
 from .floodvit import _infer_hp, vit_param_spec
 from .runtime import require_gpu
 
@@ -130,12 +130,10 @@ class MAE(ArenaModule):
             state_dict.pop(prefix + alias, None)
 
     def plan(self, B, with_backward):
-        self._ensure_arena()
-        key = (B, self.act_dtype(), bool(with_backward))
-        if key not in self._plans:
+        def build():
             from .mae_plan import MAEPlan
-            self._plans[key] = MAEPlan(self, B, self.act_dtype(), with_backward)
-        return self._plans[key]
+            return MAEPlan(self, B, self.act_dtype(), with_backward)
+        return self._cached_plan((B, self.act_dtype(), bool(with_backward)), build)
 
     def forward(self, img, rand_indices=None):
         require_gpu(img)
@@ -146,14 +144,10 @@ class MAE(ArenaModule):
         if rand_indices is None:                                 # mae.py:73
             rand_indices = torch.rand(B, self.num_patches, device=img.device).argsort(dim=-1)
         self.last_indices = rand_indices
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(B, want_grad)
         img = img.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(img, rand_indices).clone().reshape(())
-        if self._anchor is None or self._anchor.device != img.device:
-            self._anchor = torch.zeros(1, device=img.device, requires_grad=True)
-        return PlanFn.apply(self._anchor, self, plan, img, rand_indices).reshape(())
+        return self._apply_plan(plan, want_grad, img, rand_indices).reshape(())
 
 
 def build_mae(configs, precision="bf16", channels=None):

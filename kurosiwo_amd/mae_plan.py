@@ -24,7 +24,6 @@ from .plan_base import PlanBase
 
 class MAEPlan(PlanBase):
     side_tokens = os.environ.get("KSMI_SIDE_TOKENS", "1") != "0"      # plan_base.PlanBase.side_tokens (encoder and decoder layers)
-    input_names = ("img", "rand_indices")
 
     def __init__(self, model, B, dtype, with_backward):
         self._init_base(model, dtype, with_backward)

@@ -31,8 +31,8 @@ def _bump_generation(p_ptr):
 
 def _arena_of(params):
     """(base_ptr, numel) of the flat fp32 arena the tensors are views of, in order, else None.  The arena is taken from the
-    views' common storage (model.flat_params / flat_grads), so its numel is the model's own (SNUNet aligns its views to 4
-    floats, ArenaModule to 8: the padding between views belongs to the arena and the optimiser state must cover it, or the
+    views' common storage (model.flat_params / flat_grads), so its numel is the model's own (ArenaModule.ARENA_ALIGN: views
+    aligned to 8 floats, SNUNet_ECAM's to 4: the padding between views belongs to the arena and the optimiser state must cover it, or the
     autograd path (`opt.step()`) and the fused path (`step_arena`) would disagree on the state size and reset it)."""
     params = list(params)
     if not params or params[0].dtype != torch.float32:

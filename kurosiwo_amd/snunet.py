@@ -15,12 +15,14 @@ MI355X-first design:
 There is no CPU/eager fallback: a CPU tensor raises.
 """
 import math
+import os
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from .arena import ArenaModule, bn_spec
 from .runtime import require_gpu
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
@@ -43,11 +45,32 @@ def _blocks(n, c):
     ]
 
 
-class _Holder(nn.Module):
-    """Parameter/buffer container that only exists to reproduce the reference's key names."""
+def snunet_specs(in_channels, out_ch, n):
+    """(params, fp32 buffers, int64 counters) keyed and ordered as the reference's state dict."""
+    p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
+    for item in _blocks(n, in_channels):
+        if item[0] == "block":
+            _, name, cin, cout = item
+            for conv, bn, ci in (("conv1", "bn1", cin), ("conv2", "bn2", cout)):
+                p[f"{name}.{conv}.weight"] = (cout, ci, 3, 3)
+                p[f"{name}.{conv}.bias"] = (cout,)
+                bn_spec(p, b, c, f"{name}.{bn}", cout)
+        else:
+            _, name, ch = item
+            p[f"{name}.up.weight"] = (ch, ch, 2, 2)
+            p[f"{name}.up.bias"] = (ch,)
+    p["ca.fc1.weight"] = (4 * n // 16, 4 * n, 1, 1)
+    p["ca.fc2.weight"] = (4 * n, 4 * n // 16, 1, 1)
+    p["ca1.fc1.weight"] = (n // 4, n, 1, 1)
+    p["ca1.fc2.weight"] = (n, n // 4, 1, 1)
+    p["conv_final.weight"] = (out_ch, 4 * n, 1, 1)
+    p["conv_final.bias"] = (out_ch,)
+    return p, b, c
 
 
-class SNUNet_ECAM(nn.Module):
+class SNUNet_ECAM(ArenaModule):
+    ARENA_ALIGN = 4            # no bf16 mirror; the layout is kept so that dumps and checkpoints of flat_params compare with earlier builds
+
     def __init__(self, in_channels, out_ch, base_channel=32, precision="bf16"):
         super().__init__()
         if out_ch != 3:
@@ -56,39 +79,9 @@ class SNUNet_ECAM(nn.Module):
         self.precision = precision            # "bf16" (performance) | "fp32" (parity)
         # optional: BatchNorm statistics over the global batch under data parallelism (snunet_plan.SNUNetPlan.sync_bn; KSMI_SYNC_BN=1 or
         # configs["sync_bn"]); default = the reference's per-process BatchNorm
-        import os as _os
-        self.sync_bn = _os.environ.get("KSMI_SYNC_BN", "0") == "1"
-        n = base_channel
-        self._pspec, self._bspec, self._ispec = OrderedDict(), OrderedDict(), OrderedDict()
-        for item in _blocks(n, in_channels):
-            if item[0] == "block":
-                _, name, cin, cout = item
-                self._pspec[f"{name}.conv1.weight"] = (cout, cin, 3, 3)
-                self._pspec[f"{name}.conv1.bias"] = (cout,)
-                self._pspec[f"{name}.bn1.weight"] = (cout,)
-                self._pspec[f"{name}.bn1.bias"] = (cout,)
-                self._pspec[f"{name}.conv2.weight"] = (cout, cout, 3, 3)
-                self._pspec[f"{name}.conv2.bias"] = (cout,)
-                self._pspec[f"{name}.bn2.weight"] = (cout,)
-                self._pspec[f"{name}.bn2.bias"] = (cout,)
-                for bn in ("bn1", "bn2"):
-                    self._bspec[f"{name}.{bn}.running_mean"] = (cout,)
-                    self._bspec[f"{name}.{bn}.running_var"] = (cout,)
-                    self._ispec[f"{name}.{bn}.num_batches_tracked"] = ()
-            else:
-                _, name, ch = item
-                self._pspec[f"{name}.up.weight"] = (ch, ch, 2, 2)
-                self._pspec[f"{name}.up.bias"] = (ch,)
-        self._pspec["ca.fc1.weight"] = (4 * n // 16, 4 * n, 1, 1)
-        self._pspec["ca.fc2.weight"] = (4 * n, 4 * n // 16, 1, 1)
-        self._pspec["ca1.fc1.weight"] = (n // 4, n, 1, 1)
-        self._pspec["ca1.fc2.weight"] = (n, n // 4, 1, 1)
-        self._pspec["conv_final.weight"] = (out_ch, 4 * n, 1, 1)
-        self._pspec["conv_final.bias"] = (out_ch,)
-        self._build_arenas(torch.device("cpu"))
+        self.sync_bn = os.environ.get("KSMI_SYNC_BN", "0") == "1"
+        self._setup_arena(*snunet_specs(in_channels, out_ch, base_channel))
         self._init_parameters()
-        self._plans = {}
-        self._anchor = None
         self._raw_norm = None
         self._raw_version = 0          # bumped whenever the pipeline values change: part of the plan cache key
 
@@ -130,99 +123,17 @@ class SNUNet_ECAM(nn.Module):
         base, step = self._raw_norm.data_ptr(), self.in_channels * 4
         return base, base + step, base + 2 * step
 
-    # ------------------------------------------------------------------ arenas
-    @staticmethod
-    def _numel(shape):
-        r = 1
-        for s in shape:
-            r *= s
-        return r
-
-    def _holder(self, path):
-        mod = self
-        for part in path:
-            if not hasattr(mod, part):
-                setattr(mod, part, _Holder())
-            mod = getattr(mod, part)
-        return mod
-
-    def _build_arenas(self, device, old=None):
-        """(Re)create the flat arenas on `device` and (re)register every parameter/buffer as a view."""
-        def layout(spec, align):
-            offs, o = OrderedDict(), 0
-            for k, shp in spec.items():
-                offs[k] = o
-                o += -(-max(self._numel(shp), 1) // align) * align
-            return offs, o
-        self._poff, pn = layout(self._pspec, 4)        # 16-byte aligned views
-        self._boff, bn = layout(self._bspec, 4)
-        self._ioff, inn = layout(self._ispec, 1)
-        self.flat_params = torch.zeros(pn, dtype=torch.float32, device=device)
-        self.flat_grads = torch.zeros(pn, dtype=torch.float32, device=device)
-        self.flat_buffers = torch.zeros(bn, dtype=torch.float32, device=device)
-        self.flat_counters = torch.zeros(inn, dtype=torch.int64, device=device)
-        order = []
-        for item in _blocks(self.base_channel, self.in_channels):
-            name = item[1]
-            if item[0] == "block":
-                order += [(f"{name}.conv1", ["weight", "bias"], []),
-                          (f"{name}.bn1", ["weight", "bias"], ["running_mean", "running_var", "num_batches_tracked"]),
-                          (f"{name}.conv2", ["weight", "bias"], []),
-                          (f"{name}.bn2", ["weight", "bias"], ["running_mean", "running_var", "num_batches_tracked"])]
-            else:
-                order += [(f"{name}.up", ["weight", "bias"], [])]
-        order += [("ca.fc1", ["weight"], []), ("ca.fc2", ["weight"], []), ("ca1.fc1", ["weight"], []),
-                  ("ca1.fc2", ["weight"], []), ("conv_final", ["weight", "bias"], [])]
-        for path, pnames, bnames in order:
-            h = self._holder(path.split("."))
-            for pn_ in pnames:
-                key = f"{path}.{pn_}"
-                shp = self._pspec[key]
-                view = self.flat_params[self._poff[key]:self._poff[key] + self._numel(shp)].view(shp)
-                if old is not None:
-                    view.copy_(old[key])
-                if pn_ in h._parameters and h._parameters[pn_] is not None:
-                    h._parameters[pn_].data = view
-                else:
-                    h.register_parameter(pn_, nn.Parameter(view))
-            for bn_ in bnames:
-                key = f"{path}.{bn_}"
-                if bn_ == "num_batches_tracked":
-                    view = self.flat_counters[self._ioff[key]:self._ioff[key] + 1].view(())
-                else:
-                    shp = self._bspec[key]
-                    view = self.flat_buffers[self._boff[key]:self._boff[key] + shp[0]]
-                if old is not None:
-                    view.copy_(old[key])
-                h._buffers[bn_] = view
-        self._arena_device = device
-        self._plans = {}
-
-    def _arena_ok(self):
-        p0 = self.conv0_0.conv1.weight
-        pl = self.conv_final.bias
-        b0 = self.conv0_0.bn1.running_mean
-        return (p0.data_ptr() == self.flat_params.data_ptr() + 4 * self._poff["conv0_0.conv1.weight"]
-                and pl.data_ptr() == self.flat_params.data_ptr() + 4 * self._poff["conv_final.bias"]
-                and b0.data_ptr() == self.flat_buffers.data_ptr() + 4 * self._boff["conv0_0.bn1.running_mean"]
-                and p0.device == self.flat_params.device)
-
-    def _ensure_arena(self):
-        if not self._arena_ok():
-            old = {k: v.detach().clone() for k, v in self.state_dict().items()}
-            self._build_arenas(self.conv0_0.conv1.weight.device, old)
-
     def _init_parameters(self):
         """snunet.py:110-115: kaiming_normal_(fan_out, relu) on every nn.Conv2d weight, BN gamma=1
         beta=0; conv biases and ConvTranspose2d keep the PyTorch default init."""
         with torch.no_grad():
             for key, shp in self._pspec.items():
-                p = self.flat_params[self._poff[key]:self._poff[key] + self._numel(shp)].view(shp)
+                p = self._p(key).view(shp)
                 if ".up." in key:
                     if key.endswith("weight"):
                         nn.init.kaiming_uniform_(p, a=math.sqrt(5))
                     else:
-                        fan_in = shp[0] * 4 if False else self._pspec[key.replace("bias", "weight")][1] * 4
+                        fan_in = self._pspec[key.replace("bias", "weight")][1] * 4
                         p.uniform_(-1 / math.sqrt(fan_in), 1 / math.sqrt(fan_in))
                 elif ".bn" in key:
                     p.fill_(1.0 if key.endswith("weight") else 0.0)
@@ -232,42 +143,21 @@ class SNUNet_ECAM(nn.Module):
                     w = self._pspec[key.replace("bias", "weight")]
                     fan_in = w[1] * w[2] * w[3]
                     p.uniform_(-1 / math.sqrt(fan_in), 1 / math.sqrt(fan_in))
-            for key, shp in self._bspec.items():
-                b = self.flat_buffers[self._boff[key]:self._boff[key] + shp[0]]
-                b.fill_(1.0 if key.endswith("running_var") else 0.0)
-
-    # views used by the plan
-    def _p(self, key):
-        shp = self._pspec[key]
-        return self.flat_params[self._poff[key]:self._poff[key] + self._numel(shp)]
-
-    def _g(self, key):
-        shp = self._pspec[key]
-        return self.flat_grads[self._poff[key]:self._poff[key] + self._numel(shp)]
-
-    def _b(self, key):
-        return self.flat_buffers[self._boff[key]:self._boff[key] + self._bspec[key][0]]
-
-    def _c(self, key):
-        return self.flat_counters[self._ioff[key]:self._ioff[key] + 1]
-
-    def act_dtype(self):
-        return torch.bfloat16 if self.precision == "bf16" else torch.float32
 
     # ------------------------------------------------------------------ forward
     def plan(self, B, H, W, training, with_backward, tail=0):
-        self._ensure_arena()
         # the key carries a version counter, not id(tensor): _raw_ptrs() moves the tensor to the device (a new object), and a freed
         # tensor's id can be handed out again
         key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward), None if self._raw_norm is None else self._raw_version, tail,
                bool(self.sync_bn))
-        if key not in self._plans:
+
+        def build():
             from .snunet_plan import SNUNetPlan
             plan = SNUNetPlan(self, B, H, W, self.act_dtype(), training, with_backward, tail=tail, sync_bn=self.sync_bn)
             if self._raw_norm is not None:
                 plan.keep.append(self._raw_norm)   # the plan's launches hold data_ptr()s into it
-            self._plans[key] = plan
-        return self._plans[key]
+            return plan
+        return self._cached_plan(key, build)
 
     def forward(self, xA, xB, dem=None):
         """xA, xB: the two dates [B,C,H,W].  dem (optional, [B,Cd,H,W]): channels shared by both dates; forward(xA, xB, dem) equals
@@ -281,44 +171,7 @@ class SNUNet_ECAM(nn.Module):
         B, _, H, W = xA.shape
         if H % 16 or W % 16:
             raise ValueError("H and W must be multiples of 16 (four 2x2 max-pools)")
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(B, H, W, self.training, want_grad, tail)
-        xA = xA.contiguous().float()
-        xB = xB.contiguous().float()
-        dem = None if dem is None else dem.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(xA, xB, dem).clone()
-        if self._anchor is None or self._anchor.device != xA.device:
-            self._anchor = torch.zeros(1, device=xA.device, requires_grad=True)
-        return _SNUNetFn.apply(self._anchor, xA, xB, dem, self, plan)
-
-
-class _SNUNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, anchor, xA, xB, dem, model, plan):
-        from .arena import stamp_forward
-        ctx.model, ctx.plan = model, plan
-        ctx.gen = stamp_forward(plan)
-        return plan.run_forward(xA, xB, dem).clone()
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        from .arena import check_forward_stamp
-        model, plan = ctx.model, ctx.plan
-        check_forward_stamp(plan, ctx.gen)
-        params = list(model.parameters())
-        if any(p.grad is not None for p in params):
-            raise _lib.KsmiError("gradient accumulation across backward() calls is not supported by the HIP SNUNet: "
-                                 "call optimizer.zero_grad(set_to_none=True) (the PyTorch default) before each step")
-        plan.run_backward(dlogits.contiguous().float())
-        for key in model._pspec:
-            mod = model
-            parts = key.split(".")
-            for part in parts[:-1]:
-                mod = getattr(mod, part)
-            p = mod._parameters[parts[-1]]
-            if p.requires_grad:
-                p.grad = model._g(key).view(model._pspec[key])
-        return None, None, None, None, None, None
-
-
+        return self._apply_plan(plan, want_grad, xA.contiguous().float(), xB.contiguous().float(),
+                                None if dem is None else dem.contiguous().float())

@@ -7,13 +7,13 @@ oracle/unet_ref.py for the layer list) with the same constructor keywords and th
 (182 keys, 14.33 M parameters at 2 input channels).  PARITY UNPINNED: there is nothing to import; ImageNet weights
 (`encoder_weights="imagenet"`) would need the network and are refused.
 """
-import math
+import functools
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
-from .arena import ArenaModule
+from .arena import ArenaModule, bn_spec
 from .runtime import require_gpu
 
 LAYERS = ((64, 1), (128, 2), (256, 2), (512, 2))
@@ -22,13 +22,7 @@ DECODER_CHANNELS = (256, 128, 64, 32, 16)
 
 def unet_specs(in_channels, classes):
     p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
-
-    def bn(name, ch):
-        p[f"{name}.weight"] = (ch,)
-        p[f"{name}.bias"] = (ch,)
-        b[f"{name}.running_mean"] = (ch,)
-        b[f"{name}.running_var"] = (ch,)
-        c[f"{name}.num_batches_tracked"] = ()
+    bn = functools.partial(bn_spec, p, b, c)
     p["encoder.conv1.weight"] = (64, in_channels, 7, 7)
     bn("encoder.bn1", 64)
     cin = 64
@@ -84,27 +78,18 @@ class Unet(ArenaModule):
                     torch.nn.init.kaiming_uniform_(p, mode="fan_in", nonlinearity="relu")          # smp initialize_decoder
                 else:
                     torch.nn.init.xavier_uniform_(p)                                               # smp initialize_head
-            for key in self._bspec:
-                self._b(key).fill_(1.0 if key.endswith("running_var") else 0.0)
 
     def plan(self, B, H, W, training, with_backward):
-        self._ensure_arena()
-        key = (B, H, W, self.act_dtype(), bool(training), bool(with_backward))
-        if key not in self._plans:
+        def build():
             from .unet_plan import UnetPlan
-            self._plans[key] = UnetPlan(self, B, H, W, self.act_dtype(), training, with_backward)
-        return self._plans[key]
+            return UnetPlan(self, B, H, W, self.act_dtype(), training, with_backward)
+        return self._cached_plan((B, H, W, self.act_dtype(), bool(training), bool(with_backward)), build)
 
     def forward(self, x):
         require_gpu(x)
         if x.dim() != 4 or x.shape[1] != self.in_channels or x.shape[2] % 32 or x.shape[3] % 32:
             raise ValueError(f"expected [B,{self.in_channels},H,W] with H, W multiples of 32, got {tuple(x.shape)}")
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        want_grad = self._wants_grad()
         plan = self.plan(x.shape[0], x.shape[2], x.shape[3], self.training, want_grad)
         x = x.contiguous().float()
-        if not want_grad:
-            return plan.run_forward(x).clone()
-        if self._anchor is None or self._anchor.device != x.device:
-            self._anchor = torch.zeros(1, device=x.device, requires_grad=True)
-        from .arena import PlanFn
-        return PlanFn.apply(self._anchor, self, plan, x)
+        return self._apply_plan(plan, want_grad, x)

@@ -151,8 +151,6 @@ class ResNetPlan(ConvPlan):
 
 
 class UnetPlan(ResNetPlan):
-    input_names = ("x",)
-
     def __init__(self, model, B, H, W, dtype, training, with_backward):
         self._init_conv(model, B, H, W, dtype, training, with_backward)
         self.cin, self.nc = model.in_channels, model.classes

@@ -292,6 +292,37 @@ def test_backward_of_an_overwritten_forward_is_refused():
     assert all(p.grad is not None for p in model.parameters())
 
 
+def test_forward_route_with_the_dem_tail_equals_the_concatenated_inputs(dev):
+    """forward() -> loss.backward() -> opt.step() through the whole-model autograd node, as model(cat(xA, dem), cat(xB, dem)) (dem = None
+    is then one of the node's inputs) and as model(xA, xB, dem): the tail is a second source pointer of the same image load of
+    conv0_0.conv1 (same fp32 operations in the same order, as tests/test_gpu_input_pipeline.py holds for raw tiles), so logits, every
+    gradient and the parameters after one Adam step are bit-equal; the gradients are views of the flat arena in both forms."""
+    from kurosiwo_amd.loss import BCEandDiceLoss
+    from kurosiwo_amd.optim import FusedAdam
+    c, bc, B, H, W = 3, 16, 2, 32, 48
+    xA, xB = sar_like("tailA", (B, c - 1, H, W)).to(dev), sar_like("tailB", (B, c - 1, H, W)).to(dev)
+    dem = sar_like("tailD", (B, 1, H, W)).to(dev)
+    lbl = seeded_labels("tailL", (B, H, W)).to(dev)
+    sd = seeded_fill_(R.new_state_dict(c, 3, bc))
+    res = []
+    for inputs in ((torch.cat((xA, dem), 1), torch.cat((xB, dem), 1)), (xA, xB, dem)):
+        m = _model(c, bc, "fp32", sd, dev).train()
+        opt = FusedAdam(m.parameters(), lr=1e-3)
+        opt.zero_grad()
+        logits = m(*inputs)
+        BCEandDiceLoss(CLASS_WEIGHTS, 3, True)(logits, lbl).backward()
+        for k in m._pspec:
+            assert m._param_obj(k).grad.data_ptr() == m.flat_grads.data_ptr() + 4 * m._poff[k], k
+        grads = m.flat_grads.clone()
+        before = m.flat_params.clone()
+        opt.step()
+        torch.cuda.synchronize()
+        assert torch.isfinite(logits).all() and float(grads.abs().max()) > 0 and not torch.equal(before, m.flat_params)
+        res.append((logits.detach().clone(), grads, m.flat_params.clone(), m.flat_buffers.clone(), m.flat_counters.clone()))
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("precision,B,H,W,bc", [("bf16", 4, 64, 64, 32), ("fp32", 2, 32, 48, 16), ("fp32", 8, 224, 224, 32), ("bf16", 32, 224, 224, 32)])
 def test_fused_batchnorm_glue_equals_the_separate_launches(dev, precision, B, H, W, bc):
     """csrc/bnfused.hip (statistics finish inside the consuming pass: ksmi_bn_fin_add_relu with the encoder's max-pool,

@@ -10,9 +10,17 @@ convolutional plans fit in host memory; SNUNet also with base_channel 16 at 32 x
 Scalars are literal.  A descriptor passed by reference (ConvDesc, WgradDesc, ...) and the pack / row-sum descriptor tables are
 expanded field by field.  Every address, top-level or inside a descriptor, is replaced by the order of its first appearance in the
 plan's dump (@0, @1, ...): aliasing and buffer reuse stay visible, absolute addresses do not.  Then `param_ready` and the scratch
-table `_need`.  Not a test: every performance change legitimately alters the output."""
+table `_need`.  Not a test: every performance change legitimately alters the output.
+
+  python tools/plan_fingerprint.py --arenas > arenas.txt
+
+dumps the parameter arenas instead, for refactors of the model classes that must not move a parameter: every model above (one
+precision: the arenas are fp32 either way) plus SNUNet at three more (in_channels, base_channel), each built under
+torch.manual_seed(999): the arena lengths, every state_dict() entry in order (key, dtype, shape, sha256 of its bytes) and the
+offset tables `_poff`, `_boff`, `_ioff`."""
 import argparse
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -145,11 +153,43 @@ def models(family, precision):
 FAMILIES = ("snunet", "changeformer", "unet", "siam-conc", "bit-cd", "floodvit", "mae", "siam-diff", "bit-cd-variants")
 
 
+def arena_models(family):
+    yield from ((title, model) for title, model, _, _ in models(family, "bf16"))
+    if family == "snunet":
+        from kurosiwo_amd.snunet import SNUNet_ECAM
+        for c, n in ((3, 16), (4, 8), (1, 32)):
+            yield f"snunet c{c} bc{n}", SNUNet_ECAM(c, 3, base_channel=n)
+
+
+def dump_arenas(families, out):
+    for family in families:
+        it = arena_models(family)
+        while True:
+            torch.manual_seed(999)                                 # (the generator builds the next model inside next())
+            try:
+                title, model = next(it)
+            except StopIteration:
+                break
+            out.write(f"==== {title}: params {model.flat_params.numel()} buffers {model.flat_buffers.numel()} "
+                      f"counters {model.flat_counters.numel()}\n")
+            for k, v in model.state_dict().items():
+                digest = hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()
+                out.write(f"{k} {v.dtype} {tuple(v.shape)} {digest}\n")
+            for name in ("_poff", "_boff", "_ioff"):
+                out.write(f"-- {name}\n")
+                for k, o in getattr(model, name).items():
+                    out.write(f"{k} {o}\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--families", default=",".join(FAMILIES))
+    ap.add_argument("--arenas", action="store_true", help="dump the parameter arenas (CPU) instead of the launch lists")
     args = ap.parse_args()
+    if args.arenas:
+        dump_arenas(args.families.split(","), sys.stdout)
+        return
     dev = torch.device(args.device)
     for family in args.families.split(","):
         for precision in ("bf16", "fp32"):
