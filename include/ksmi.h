@@ -677,6 +677,27 @@ int ksmi_token_cross_backward(const void* x, const float* gamma, const float* be
  * 193-198) on raw backscatter tiles already in HBM; x, y NCHW fp32 (y may alias x).  clamp_input < 0: Normalize only (the SLC class,
  * dataset/Dataset.py:1081-1085, neither clamps nor replaces NaNs) */
 int ksmi_sar_preprocess(const float* x, const float* mean, const float* stdv, float* y, int B, int C, int64_t HW, float clamp_input, void* stream);
+/* Augmentation views on the device (csrc/augment.hip; dataset/Dataset.py:171-190, 792-805, 864-983, utilities/augmentations.py):
+ * RandomResizedCrop(224, interpolation = 3: cv2.INTER_AREA, which enlarges with two taps and "area" coefficients) -> flips ->
+ * per-pixel ops, fused with the clamp -> nan_to_num -> Normalize of ksmi_sar_preprocess.  x, y NCHW fp32 [B][C][224][224], y != x.
+ * params: device table, one int32 row {y0, x0, h, w, flip_h, flip_v} per sample (rows are forced inside the tile by the kernel);
+ * the row {0, 0, 224, 224, 0, 0} is bit-identical to ksmi_sar_preprocess.
+ * fallback: NULL, or B device words written by ksmi_augment_masks(count): a sample whose word is 0 takes the identity row and no
+ * per-pixel op (the reference keeps the un-augmented sample when the augmented valid mask is empty) -- no host sync.
+ * Per-pixel ops on the counter-based stream of the dropout family (rng_state = {seed, step}, see ksmi_rng_advance): op_order holds up
+ * to three 2-bit slots, first op in the low bits: 1 MultiplicativeNoise (one factor ~ U[mult_lo, mult_hi) per sample), 2 GaussNoise
+ * (var ~ U[gauss_var_lo, gauss_var_hi) per sample, N(0, var) per element), 3 CoarseDropout (cut_holes holes of cut_h x cut_w, filled
+ * with 0 before Normalize, the same in every channel); *_thr = round(p * 2^32): a sample gets the op when its draw < thr.
+ * op_order = 0: none, rng_state may be NULL.
+ *   ksmi_augment_masks: the cv2.INTER_NEAREST view of [B][224][224] planes of elem_bytes = 1, 4 or 8 (labels, valid masks; moved as
+ *   bits) under the same table; y may be NULL (count only); count: NULL, or B words that receive the number of non-zero elements of
+ *   each view (zeroed on the stream first). */
+int ksmi_augment_views(const float* x, const int32_t* params, const int32_t* fallback, const float* mean, const float* stdv, float* y, int B, int C,
+                       int H, int W, float clamp_input, uint32_t mult_thr, float mult_lo, float mult_hi, uint32_t gauss_thr, float gauss_var_lo,
+                       float gauss_var_hi, uint32_t cut_thr, int cut_holes, int cut_h, int cut_w, int op_order, const uint32_t* rng_state,
+                       void* stream);
+int ksmi_augment_masks(const void* x, void* y, const int32_t* params, const int32_t* fallback, int32_t* count, int B, int H, int W, int elem_bytes,
+                       void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -41,6 +41,8 @@ def prepare_loaders(configs):
         raise SystemExit(2)
     bs, workers = configs["batch_size"], configs.get("num_workers", 0)
     archive = archive_kind(configs)
+    if configs.get("data_augmentations") and "augmentations" not in configs:
+        configs.update(load_augmentation_config(configs))                    # utilities/utilities.py:369-374
     if archive is not None:
         return _archive_loaders(configs, archive, bs, workers)
     from . import distributed as D
@@ -52,6 +54,18 @@ def prepare_loaders(configs):
     print("Samples in Val Set: ", len(ds["val"]))
     print("Samples in Test Set: ", len(ds["test"]))
     return tr, va, te
+
+
+def load_augmentation_config(configs=None):
+    """configs/augmentations/augmentation.json (or configs["augmentation_config"]) -> {"augmentations": {...}}"""
+    import os
+    from .config import load_json5
+    path = (configs or {}).get("augmentation_config")
+    if path is None:
+        path = os.path.join("configs", "augmentations", "augmentation.json")
+        if not os.path.isfile(path):                                         # not started from the repository root
+            path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), path)
+    return load_json5(path)
 
 
 def archive_kind(configs):
@@ -88,15 +102,25 @@ def _archive_loaders(configs, kind, bs, workers):
     print("Initializing ", configs["track"])
     print("=" * 20)
     cls = DS.SLCDataset if kind == "slc" else DS.Dataset
-    ds = {m: cls(mode=m, configs=configs) for m in ("train", "val", "test")}
+    pipeline = None
+    if configs.get("data_augmentations"):
+        # the views are made by the batch-level loader of the train split (kurosiwo_amd/augment.py); the per-sample classes have no
+        # augmented path, so the train Dataset is built from a copy of the configs with the flag cleared
+        from .augment import build_pipeline
+        pipeline = build_pipeline(configs["augmentations"])
+    plain = dict(configs, data_augmentations=False) if pipeline is not None else configs
+    ds = {m: cls(mode=m, configs=plain) for m in ("train", "val", "test")}
     batch_level = ((kind == "slc" or configs.get("clamp_input") is not None) and configs.get("scale_input") == "normalize"
                    and not configs.get("uint8") and not configs.get("slope") and not configs.get("oversampling")
                    and configs.get("gpu_input_pipeline", True) and str(configs.get("device", "cuda")).startswith("cuda")
                    and torch.cuda.is_available())
+    if pipeline is not None and not (batch_level and kind == "grd"):
+        raise NotImplementedError("albumentations views / per-date diffusion records are outside this build (SURVEY.md §2)")
     if batch_level:
         mk = lambda m, shuffle, drop: DS.TileBatchLoader(ds[m], bs, shuffle=shuffle, drop_last=drop, device=configs.get("device", "cuda"),
                                                          threads=_loader_threads(configs, D.world_size()), rank=D.get_rank(), world=D.world_size(),
-                                                         seed=configs.get("seed", 999) if shuffle else None)
+                                                         seed=configs.get("seed", 999) if shuffle else None,
+                                                         augment=pipeline if m == "train" else None)
     else:
         mk = lambda m, shuffle, drop: D.make_loader(ds[m], bs, shuffle, drop, workers, seed=configs.get("seed", 999))
     tr, va, te = mk("train", True, True), mk("val", False, False), mk("test", False, False)
@@ -120,3 +144,25 @@ def preprocess_gpu(raw, mean, std, clamp_input=0.15, out=None):
     _lib.check(_lib.load().ksmi_sar_preprocess(raw.data_ptr(), m.data_ptr(), s.data_ptr(), out.data_ptr(), B, Cc, H * W, float(clamp_input), stream_ptr()),
                "sar_preprocess")
     return out
+
+
+def ssl_archive(configs):
+    """True when the MAE pre-training archive (configs["root_path"]/data) is on disk; KSMI_DATA as in archive_kind"""
+    import os
+    want = os.environ.get("KSMI_DATA", "")
+    if want == "synthetic":
+        return False
+    found = bool(configs.get("root_path")) and os.path.isdir(os.path.join(configs["root_path"], "data"))
+    if not found and want == "archive":
+        raise FileNotFoundError("KSMI_DATA=archive but configs['root_path']/data is not on disk")
+    return found
+
+
+def ssl_loader(configs):
+    """dataset/Dataset.py SSLDataset + the DataLoader of training/train_mae.py:142-151 (shuffle, drop_last) as one batch-level loader"""
+    from . import dataset as DS
+    from . import distributed as D
+    ds = DS.SSLDataset(configs)
+    print("Samples in SSL Set: ", len(ds))
+    return DS.SSLBatchLoader(ds, configs["batch_size"], shuffle=True, drop_last=True, device=configs.get("device", "cuda"),
+                             threads=_loader_threads(configs, D.world_size()), rank=D.get_rank(), world=D.world_size(), seed=configs.get("seed", 999))

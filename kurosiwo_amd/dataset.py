@@ -9,9 +9,13 @@ tile reader (kurosiwo_amd/geotiff.py -> ksmi_tiff_* / ksmi_tile_batch_read), plu
 MK0_MNA, MK0_DEM) and the tuple `__getitem__` returns (dataset/Dataset.py:824-860), so torch's DataLoader works on them exactly as
 in the reference; `TileBatchLoader` yields the same tuple, collated, with the images already on the device.
 
-Not carried over (need packages that are not in the image): albumentations views (`data_augmentations`, task
-"self-supervised" of Dataset.create_views), scale_input == "custom" (torchio RescaleIntensity), the "diffusion-unsup" per-date
-records.  They raise NotImplementedError instead of silently doing something else."""
+Augmentation views (kurosiwo_amd/augment.py, csrc/augment.hip) are a property of the BATCH loaders: `SSLDataset` / `SSLBatchLoader`
+serve the MAE pre-training views of dataset/Dataset.py:864-983, `TileBatchLoader(..., augment=pipeline)` the supervised
+`data_augmentations` of Dataset.create_views (:171-190, :792-805), both rendered on the device from a per-sample parameter table.
+
+Not carried over (need packages that are not in the image): an augmented path inside the per-sample `Dataset` class
+(`data_augmentations`, task "self-supervised" there), scale_input == "custom" (torchio RescaleIntensity), the "diffusion-unsup"
+per-date records.  They raise NotImplementedError instead of silently doing something else."""
 import bz2
 import gzip
 import lzma
@@ -379,6 +383,93 @@ class SLCDataset(_Records, torch.utils.data.Dataset):
         return (flood, mask, sec1, sec2) + tail
 
 
+SSL_MEAN, SSL_STD = (0.0953, 0.0264), (0.0427, 0.0215)          # dataset/Dataset.py:968-970: all of Kuro Siwo, labeled + unlabeled
+
+
+class SSLDataset(torch.utils.data.Dataset):
+    """MAE pre-training samples: dataset/Dataset.py:864-983.  Every grid-cell folder under root_path/data is a sample (no pickle, no
+    activation lists); an item is (image_view [6,224,224], flood, pre_event_1, pre_event_2), the view a RandomResizedCrop(224,
+    scale=(0.2, 1.0), interpolation=3) + HorizontalFlip(0.5) of the six channels in the order flood, pre1, pre2.
+
+    Differences, on purpose: the sample cache `ssl_samples.pkl` is written under configs["checkpoint_path"] or to `cache=` (the
+    reference drops it into the working directory); directory listings are sorted before the Random(999) shuffle, so the order does
+    not depend on the file system; a folder that holds files is listed once (the reference appends it once per file); the view is
+    rendered from the raw tiles by kurosiwo_amd.augment.apply_cpu -- clamp, resize, then Normalize, where the reference resizes the
+    normalised tiles: Normalize is affine and the resize a convex combination, so the two agree to fp32 rounding; the view
+    parameters come from a seeded random.Random (augment.sample_resized_crop), not from Python's global stream."""
+
+    def __init__(self, configs=None, cache=None, seed=None):
+        from . import augment
+        if set(configs["channels"]) != {"vv", "vh"}:
+            raise ValueError("SSLDataset: channels vv + vh (the reference normalises with a two-channel mean / std)")
+        self.pipeline = augment.Pipeline(crop=(1.0, (0.2, 1.0), (3 / 4, 4 / 3)), hflip=0.5)
+        self.root_path = os.path.join(configs["root_path"], "data")
+        self.configs = configs
+        if cache is None:
+            if not configs.get("checkpoint_path"):
+                raise ValueError("SSLDataset: pass cache= or set configs['checkpoint_path'] (where ssl_samples.pkl is kept)")
+            cache = os.path.join(configs["checkpoint_path"], "ssl_samples.pkl")
+        self.cache = cache
+        if os.path.isfile(cache):
+            with open(cache, "rb") as f:
+                self.samples = pickle.load(f)
+        else:
+            self.samples = self.walk(self.root_path)
+            os.makedirs(os.path.dirname(os.path.abspath(cache)), exist_ok=True)
+            with open(cache, "wb") as f:
+                pickle.dump(self.samples, f)
+        random.Random(999).shuffle(self.samples)
+        self.num_examples = len(self.samples)
+        self.rng = random.Random(configs.get("seed", 999) if seed is None else seed)       # view parameters of __getitem__
+        self.mean, self.std = list(SSL_MEAN), list(SSL_STD)
+
+    @staticmethod
+    def walk(root):
+        """dataset/Dataset.py:874-894: event / aoi (".gpkg" skipped) / grid / hash; a hash level that holds files means the grid folder
+        itself is the sample"""
+        samples = []
+        for event in sorted(os.listdir(root)):
+            folder_dir = os.path.join(root, event)
+            for folder in sorted(os.listdir(folder_dir)):
+                if ".gpkg" in folder:
+                    continue
+                subfolder_dir = os.path.join(folder_dir, folder)
+                for subfolder in sorted(os.listdir(subfolder_dir)):
+                    hashes_dir = os.path.join(subfolder_dir, subfolder)
+                    flat = False
+                    for hash_folder in sorted(os.listdir(hashes_dir)):
+                        hash_folder_dir = os.path.join(hashes_dir, hash_folder)
+                        if os.path.isfile(hash_folder_dir):
+                            flat = True
+                        else:
+                            samples.append(hash_folder_dir)
+                    if flat:
+                        samples.append(hashes_dir)
+        return samples
+
+    def __len__(self):
+        return self.num_examples
+
+    channel_stack = Dataset.channel_stack
+    concat = Dataset.concat
+
+    def sample_paths(self, index):
+        files = _tile_files(self.samples[index])
+        return [files[p] for p in SAR_PREFIXES]
+
+    def __getitem__(self, index):
+        from . import augment
+        raw = np.stack([geotiff.read(p, dtype=np.float32)[0] for p in self.sample_paths(index)])          # flood vv, vh, pre1 ..., pre2 ...
+        m = torch.as_tensor(self.mean, dtype=torch.float32).view(-1, 1, 1)
+        s = torch.as_tensor(self.std, dtype=torch.float32).view(-1, 1, 1)
+        flood, pre_event_1, pre_event_2 = ((self.concat(raw[a], raw[a + 1]) - m) / s for a in (0, 2, 4))
+        clamp = self.configs["clamp_input"]
+        src = raw if clamp is not None else np.nan_to_num(raw, nan=200.0)                                 # nan_to_num(image, 200), :925-926
+        params = self.pipeline.sample_params(self.rng, 1)
+        image = augment.apply_cpu(src[None], params, self.mean * 3, self.std * 3, clamp)[0]
+        return torch.from_numpy(image), flood, pre_event_1, pre_event_2
+
+
 class _Ragged(Exception):
     pass
 
@@ -395,6 +486,14 @@ def _collate_to(items, dev, sharded):
     return ShardedBatch(out) if sharded else tuple(out)
 
 
+class _RankSlice(list):
+    """this rank's indices of one global batch, with the size of that batch and the position of the slice in it"""
+
+    def __init__(self, idx, n_global, lo):
+        super().__init__(idx)
+        self.n_global, self.lo = n_global, lo
+
+
 class ShardedBatch(tuple):
     """a collated batch that already holds only this rank's samples (distributed.shard_batch passes it through)"""
 
@@ -407,28 +506,65 @@ class TileBatchLoader:
     (SNUNet_ECAM.set_input_pipeline); the per-channel scale lists of the tuple are what such a model needs.
     rank / world: this rank reads only its contiguous slice of every global batch (the slice distributed.shard_batch would cut).
     prefetch: batches decoded ahead by a producer thread (the native decode releases the GIL; its copy and preprocess run on a copy
-    stream of their own), 0 = decode in the consumer's thread."""
+    stream of their own), 0 = decode in the consumer's thread.
+    augment: a kurosiwo_amd.augment.Pipeline (GRD, train mode, CUDA only): the `data_augmentations` views of Dataset.create_views
+    (dataset/Dataset.py:171-190, 792-805) rendered on the device.  The three dates of a sample share one parameter row; the label and
+    the valid mask (MK0_MNA) take the nearest-neighbour view; a sample whose augmented valid mask is empty comes back un-augmented,
+    decided on the device (no host sync).  With raw=True the views are clamped but not normalised."""
 
     def __init__(self, dataset, batch_size, shuffle=False, drop_last=False, device="cuda", threads=8, raw=False, rank=0, world=1, seed=None,
-                 prefetch=2):
+                 prefetch=2, augment=None):
         cfg = dataset.configs
         self.slc = isinstance(dataset, SLCDataset)
         if not isinstance(dataset, (Dataset, SLCDataset)) or cfg["scale_input"] != "normalize" or cfg.get("uint8") or cfg.get("slope"):
             raise ValueError("TileBatchLoader: Dataset / SLCDataset with scale_input 'normalize' (no uint8, no slope)")
         if not self.slc and cfg["clamp_input"] is None:
             raise ValueError("TileBatchLoader: clamp_input is required (the GPU preprocess clamps)")
+        if augment is not None and (self.slc or dataset.mode != "train" or torch.device(device).type != "cuda" or cfg.get("oversampling")):
+            raise NotImplementedError("augmentation views run in the batch loader of the GRD train split on a CUDA device only (SURVEY.md §2)")
+        self.raw, self.augment = raw, augment
+        self.nch = len(cfg["channels"])
+        tiles = (12 if self.slc else 6) + 1 + (1 if cfg["dem"] else 0) + (1 if augment is not None else 0)
+        self._setup(dataset, batch_size, shuffle, drop_last, device, threads, rank, world, seed, prefetch, tiles, table=augment is not None)
+
+    def _setup(self, dataset, batch_size, shuffle, drop_last, device, threads, rank, world, seed, prefetch, tiles_per_sample, table=False):
+        """index order, rank slice, pinned staging buffer and copy stream (shared with SSLBatchLoader).  table: one more tile at the end
+        of the staging buffer holds the int32 view-parameter rows of a batch and the two words {seed, step} of its random stream"""
         if batch_size % world:
             raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
         self.ds, self.bs, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
-        self.device, self.threads, self.raw, self.rank, self.world = torch.device(device), threads, raw, rank, world
+        self.device, self.threads, self.rank, self.world = torch.device(device), threads, rank, world
         self.gen = random.Random(seed)
         self.dataset = dataset                      # (the trainers read loader.dataset.activations)
-        self.nch = len(cfg["channels"])
         per = batch_size // world
+        if per * 6 + 2 > TILE * TILE:
+            raise ValueError("batch too large for the parameter table")
         pin = self.device.type == "cuda"
         self.prefetch = max(0, int(prefetch))
-        self.stage = torch.empty((per * ((12 if self.slc else 6) + 1 + (1 if cfg["dem"] else 0)), TILE, TILE), dtype=torch.float32, pin_memory=pin)
+        self.stage = torch.empty((per * tiles_per_sample + (1 if table else 0), TILE, TILE), dtype=torch.float32, pin_memory=pin)
         self.copy_stream = torch.cuda.Stream(self.device) if pin else None
+        # view parameters: every rank draws the rows of the whole global batch from the same stream and keeps its slice, so the ranks'
+        # batches concatenate to the one-rank batch; the device-side stream of the per-pixel ops is rank-folded like the models' one
+        base = 999 if seed is None else seed
+        self.view_rng = random.Random(base)
+        self.rng_seed = (int(base) ^ (0x9E3779B1 * rank)) & 0xFFFFFFFF
+        self.batches_loaded = 0
+        self.last_params = None                     # int32 [n, 6] rows of the batch loaded last (inspection, tests)
+
+    def _view_table(self, pipeline, indices, at):
+        """draw the rows of the global batch `indices` is a slice of, keep that slice, write the rows and {seed, step} into the
+        staging buffer from tile `at` on; -> the float32 view of that region (the caller copies it to the device, possibly together
+        with the tiles in front of it)"""
+        n, lo = len(indices), getattr(indices, "lo", 0)
+        rows = pipeline.sample_params(self.view_rng, getattr(indices, "n_global", n))[lo:lo + n]
+        self.last_params = rows.copy()
+        self.batches_loaded += 1
+        region = self.stage.view(-1)[at * TILE * TILE:at * TILE * TILE + n * 6 + 2]
+        words = region.view(torch.int32)
+        words[:n * 6] = torch.from_numpy(rows.reshape(-1))
+        words[n * 6] = self.rng_seed - (1 << 32) if self.rng_seed >= (1 << 31) else self.rng_seed          # the uint32 word, as int32 bits
+        words[n * 6 + 1] = self.batches_loaded & 0x7FFFFFFF
+        return region
 
     def __len__(self):
         n = len(self.ds)
@@ -441,7 +577,8 @@ class TileBatchLoader:
         for b in range(len(self)):
             idx = order[b * self.bs:(b + 1) * self.bs]
             n = len(idx)
-            yield idx[n * self.rank // self.world:n * (self.rank + 1) // self.world]
+            lo = n * self.rank // self.world
+            yield _RankSlice(idx[lo:n * (self.rank + 1) // self.world], n, lo)
 
     def __iter__(self):
         if not self.prefetch:
@@ -558,6 +695,9 @@ class TileBatchLoader:
             paths += [f["MK0_DEM"] for f in files]
         with_mask = [j for j, f in enumerate(files) if "MK0_MLU" in f]           # a cell without MK0_MLU: all zeros (Dataset.py:787-789)
         paths += [files[j]["MK0_MLU"] for j in with_mask]
+        aug = self.augment
+        if aug is not None:                                       # ... [valid masks][view table]
+            paths += [f["MK0_MNA"] for f in files]
         stage = self.stage[:len(paths)]
         geotiff.read_batch(paths, TILE, TILE, out=stage, threads=self.threads)
         sar = stage[:6 * n].view(n, 6, TILE, TILE).to(dev, non_blocking=True)
@@ -581,7 +721,19 @@ class TileBatchLoader:
         else:
             raise ValueError(f"unsupported channels {ch}")
         means, stds = cfg["data_mean"], cfg["data_std"]
-        if not self.raw:
+        if aug is not None and n:
+            from . import augment as A
+            at = len(paths)
+            nwords = self._view_table(aug, indices, at).numel()                      # the table sits right behind the valid masks: one copy
+            tail = self.stage.view(-1)[(at - n) * TILE * TILE:at * TILE * TILE + nwords].to(dev, non_blocking=True)
+            valid, words = tail[:n * TILE * TILE].view(n, TILE, TILE), tail[n * TILE * TILE:].view(torch.int32)
+            table, rng_state = words[:n * 6], words[n * 6:n * 6 + 2]
+            _, alive = A.apply_masks(valid, table, count=True, write=False)       # non-zero pixels of every augmented valid mask
+            mask, _ = A.apply_masks(mask.contiguous(), table, fallback=alive)
+            m, sd = (means, stds) if not self.raw else ([0.0] * len(means), [1.0] * len(stds))
+            dates = [A.apply(d.contiguous(), table, m, sd, cfg["clamp_input"], aug, fallback=alive, rng_state=rng_state) for d in dates]
+            # (the DEM is left as it is: create_views gets the three dates and the two masks only, dataset/Dataset.py:793-796)
+        elif not self.raw:
             if dev.type != "cuda":
                 raise RuntimeError("TileBatchLoader normalises on the GPU (raw=True hands out raw tiles on any device)")
             dates = [preprocess_gpu(d, means, stds, cfg["clamp_input"]) for d in dates]
@@ -595,3 +747,35 @@ class TileBatchLoader:
                        torch.as_tensor(cfg["dem_std"], dtype=torch.float32, device=dev).view(1, -1, 1, 1))
         out += [torch.tensor([s["clz"] for s in samples], dtype=torch.int64), torch.tensor([s["activation"] for s in samples], dtype=torch.int64)]
         return ShardedBatch(out) if self.world > 1 else tuple(out)
+
+
+class SSLBatchLoader(TileBatchLoader):
+    """Batch-level loader of `SSLDataset` (the DataLoader of training/train_mae.py:142-151): the 6 x n tiles of a batch are decoded into
+    the pinned staging buffer with the view-parameter table behind them, go to the device in ONE copy, and ONE ksmi_augment_views
+    launch on the copy stream renders the normalised views.  Yields (image [n, 6, 224, 224],) -- the loop reads batch[0] only
+    (train_mae.py:57).  Index order, rank / world slicing, prefetch: as TileBatchLoader."""
+
+    def __init__(self, dataset, batch_size, shuffle=True, drop_last=True, device="cuda", threads=8, rank=0, world=1, seed=None, prefetch=2):
+        if not isinstance(dataset, SSLDataset):
+            raise ValueError("SSLBatchLoader: an SSLDataset")
+        if dataset.configs["clamp_input"] is None:
+            raise ValueError("SSLBatchLoader: clamp_input is required (the kernel clamps; SSLDataset[i] serves the un-clamped configs)")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("SSLBatchLoader renders the views on the GPU (SSLDataset[i] is the CPU path)")
+        self.slc, self.raw, self.augment = False, False, dataset.pipeline
+        self._setup(dataset, batch_size, shuffle, drop_last, device, threads, rank, world, seed, prefetch, 6, table=True)
+        self.mean = torch.tensor(dataset.mean * 3, dtype=torch.float32, device=self.device)
+        self.std = torch.tensor(dataset.std * 3, dtype=torch.float32, device=self.device)
+
+    def _load(self, indices):
+        from . import augment as A
+        ds, n = self.ds, len(indices)
+        if n == 0:
+            return (torch.empty((0, 6, TILE, TILE), dtype=torch.float32, device=self.device),)
+        paths = [p for i in indices for p in ds.sample_paths(i)]
+        geotiff.read_batch(paths, TILE, TILE, out=self.stage[:6 * n], threads=self.threads)
+        region = self._view_table(self.augment, indices, 6 * n)
+        flat = self.stage.view(-1)[:6 * n * TILE * TILE + region.numel()].to(self.device, non_blocking=True)
+        raw = flat[:6 * n * TILE * TILE].view(n, 6, TILE, TILE)
+        words = flat[6 * n * TILE * TILE:].view(torch.int32)
+        return (A.apply(raw, words[:n * 6], self.mean, self.std, ds.configs["clamp_input"], self.augment, rng_state=words[n * 6:n * 6 + 2]),)

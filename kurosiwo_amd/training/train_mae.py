@@ -8,8 +8,9 @@ one, with the loss divided by `accumulate_gradients` (:65-70, :108-122) -- Adam,
 `vit_{epoch}.pt` / `trained_vit_{epochs}.pt` (pickled encoder modules the fine-tuning config points at) and
 `mae_vit_{epochs}.pt` (encoder state dict) (:203-229).
 Changed on purpose: bf16 compute replaces torch.cuda.amp autocast + GradScaler (bf16 needs no loss scaling); the running loss is
-accumulated on the device and read once per logging interval; wandb dropped; the SSL dataset reader is out of scope
-(DESIGN.md §7), `loader` yields (image, ...) tuples and a synthetic one is built when none is passed.
+accumulated on the device and read once per logging interval; wandb dropped; `loader` yields (image, ...) tuples; when none is
+passed the archive under configs["root_path"]/data is served by kurosiwo_amd.data.ssl_loader (SSLDataset's resized-crop + flip views,
+rendered on the device), and a synthetic set is built when there is no archive (KSMI_DATA=synthetic / archive as in data.py).
 """
 import math
 import os
@@ -110,6 +111,11 @@ def train(configs, loader=None, precision="bf16"):
     accumulated = 1 if configs.get("accumulate_gradients") is None else configs["accumulate_gradients"]
     configs["lr"] = configs["learning_rate"] * accumulated                     # train_mae.py:157-160
     device = configs.get("device", configs.get("gpu"))
+    if loader is None:
+        from ..data import ssl_archive, ssl_loader
+        if ssl_archive(configs) and torch.device(device).type == "cuda":
+            loader = ssl_loader(dict(configs, device=device))
+            configs["num_channels"] = 6            # the views stack flood, pre1, pre2 (utilities.py:382: len(channels) * len(inputs))
     if loader is None:
         ds = _SyntheticSSL(max(configs["batch_size"] * 4, 8), configs["num_channels"], configs["image_size"], configs.get("seed", 999))
         loader = torch.utils.data.DataLoader(ds, batch_size=configs["batch_size"], shuffle=False, drop_last=False)
