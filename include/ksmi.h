@@ -513,6 +513,15 @@ int ksmi_attention_backward(const void* qkv, const void* out, const float* lse, 
 /* [relu ->] nn.Upsample(scale_factor=2) nearest (model_utilities.py:36-41) */
 int ksmi_upsample2_forward(const void* x, void* y, int B, int H, int W, int C, int relu, int dtype, void* stream);
 int ksmi_upsample2_backward(const void* dy, const void* x_pre, void* dx, int B, int H, int W, int C, int relu, int dtype, void* stream);
+/* the same backward for a gradient with several writers (UNet++: an upsampled tensor is also a skip): dx[B,H,W,C] = (accumulate ? dx : 0)
+ * + (x_pre > 0 if relu) * sum of the 2x2 window of dy[B,2H,2W,C]; the ReLU mask gates this writer's share only.  16-byte vectors, each dy
+ * element read once; accumulate = 0 never reads dx. */
+int ksmi_upsample2_backward_acc(const void* dy, const void* x_pre, void* dx, int accumulate, int B, int H, int W, int C, int relu, int dtype,
+                                void* stream);
+/* one pass over a convolution output z[B,H,W,C]: y = relu(z * scale[c] + shift[c]) and u[B,2H,2W,C] = the nearest x2 copy of the stored y,
+ * bit-equal to ksmi_affine(relu = 1, alpha = 1) followed by ksmi_upsample2_forward(relu = 0) */
+int ksmi_affine_relu_upsample2(const void* z, const float* scale, const float* shift, void* y, void* u, int B, int H, int W, int C, int dtype,
+                               void* stream);
 
 /* ---------------------------------------------------------------------------------
  * ChangeFormerV6 glue (models/changeformer.py); the dense contractions run on ksmi_conv_forward / ksmi_conv_wgrad.

@@ -476,6 +476,77 @@ __global__ void upsample2_bwd_kernel(const T* dy, const T* xpre, T* dx, int B, i
     *(u32x4*)(dx + v * VEC) = vec_pack<T>(s);
   }
 }
+// the same sum as a later writer of dx (UNet++: every upsampled tensor is also somebody's skip): dx = (accumulate ? dx : 0) +
+// (x_pre > 0 if relu) * sum of the 2x2 dy window.  One thread owns one 16-byte vector of dx and the complete window above it, so
+// every dy vector is read exactly once and the read-modify-write of dx stays inside one thread.
+template <typename T>
+__global__ void upsample2_bwd_acc_kernel(const T* dy, const T* xpre, T* dx, int B, int H, int W, int C, int relu, int accumulate) {
+  constexpr int VEC = ElemTraits<T>::kVec;
+  const int CV = C / VEC;
+  const int64_t n = (int64_t)B * H * W * CV;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
+    const int cv = v % CV; int64_t r = v / CV;
+    const int ix = r % W; r /= W;
+    const int iy = r % H; const int64_t b = r / H;
+    const T* w0 = dy + ((b * 2 * H + 2 * iy) * 2 * W + 2 * ix) * C + cv * VEC;       // window row 2 iy; row 2 iy + 1 is 2 W C further
+    const u32x4 q00 = *(const u32x4*)w0, q01 = *(const u32x4*)(w0 + C);
+    const u32x4 q10 = *(const u32x4*)(w0 + (int64_t)2 * W * C), q11 = *(const u32x4*)(w0 + (int64_t)2 * W * C + C);
+    float s[VEC], t[VEC];
+    vec_unpack<T>(q00, s);
+    vec_unpack<T>(q01, t);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] += t[j];
+    vec_unpack<T>(q10, t);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] += t[j];
+    vec_unpack<T>(q11, t);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) s[j] += t[j];
+    if (relu) {
+      vec_unpack<T>(*(const u32x4*)(xpre + v * VEC), t);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) if (!(t[j] > 0.f)) s[j] = 0.f;
+    }
+    if (accumulate) {
+      vec_unpack<T>(*(const u32x4*)(dx + v * VEC), t);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) s[j] += t[j];
+    }
+    *(u32x4*)(dx + v * VEC) = vec_pack<T>(s);
+  }
+}
+
+// y = relu(z * scale[c] + shift[c]) at h x w and U = nearest x2 copy of the STORED y at 2h x 2w in one pass over z (the BatchNorm apply
+// of a decoder block whose output is the next block's upsampled input): the arithmetic is affine_kernel's (cformer.hip, relu = 1,
+// alpha = 1), the vector is packed once and stored five times, so U holds y's bits.
+template <typename T>
+__global__ void affine_relu_upsample2_kernel(const T* z, const float* scale, const float* shift, T* y, T* U, int B, int H, int W, int C) {
+  constexpr int VEC = ElemTraits<T>::kVec;
+  const int CV = C / VEC;
+  const int64_t n = (int64_t)B * H * W * CV;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
+    const int cv = v % CV; int64_t r = v / CV;
+    const int ix = r % W; r /= W;
+    const int iy = r % H; const int64_t b = r / H;
+    const int c = cv * VEC;
+    float f[VEC];
+    vec_unpack<T>(*(const u32x4*)(z + v * VEC), f);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      float o = f[j];
+      o = o * scale[c + j] + shift[c + j];
+      o = fmaxf(o, 0.f);
+      f[j] = o * 1.0f;
+    }
+    const u32x4 q = vec_pack<T>(f);
+    *(u32x4*)(y + v * VEC) = q;
+    T* u0 = U + ((b * 2 * H + 2 * iy) * 2 * W + 2 * ix) * C + c;
+    *(u32x4*)u0 = q;
+    *(u32x4*)(u0 + C) = q;
+    *(u32x4*)(u0 + (int64_t)2 * W * C) = q;
+    *(u32x4*)(u0 + (int64_t)2 * W * C + C) = q;
+  }
+}
 
 // ---- MAE token shuffles (models/mae.py:73-118) ------------------------------------------------------------------------
 // gather : dst[b][j][:] = src[b][idx[b][j]][:] (+ table[idx[b][j] + table_off][:])           (:77-78, :82, :113)
@@ -880,6 +951,30 @@ int ksmi_upsample2_backward(const void* dy, const void* x_pre, void* dx, int B, 
           hipLaunchKernelGGL(upsample2_bwd_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x_pre, (bf16_t*)dx, B, H, W, C, relu),
           hipLaunchKernelGGL(upsample2_bwd_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)x_pre, (float*)dx, B, H, W, C, relu));
   return ksmi_check_launch("upsample2_bwd");
+}
+
+int ksmi_upsample2_backward_acc(const void* dy, const void* x_pre, void* dx, int accumulate, int B, int H, int W, int C, int relu, int dtype,
+                                void* stream) {
+  const int vec = dtype == KSMI_BF16 ? 8 : 4;
+  if (C < vec || C % vec || B < 1 || H < 1 || W < 1) return ksmi_fail(KSMI_E_ARG, "upsample2_bwd_acc: C must be a multiple of the vector, B, H, W >= 1");
+  if (!dy || !dx || (relu && !x_pre)) return ksmi_fail(KSMI_E_ARG, "upsample2_bwd_acc: null tensor (x_pre is required with relu)");
+  const int64_t n = (int64_t)B * H * W * (C / vec);
+  KSMI_DT(dtype,
+          hipLaunchKernelGGL(upsample2_bwd_acc_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, (const bf16_t*)x_pre, (bf16_t*)dx, B, H, W, C, relu, accumulate),
+          hipLaunchKernelGGL(upsample2_bwd_acc_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)dy, (const float*)x_pre, (float*)dx, B, H, W, C, relu, accumulate));
+  return ksmi_check_launch("upsample2_bwd_acc");
+}
+
+int ksmi_affine_relu_upsample2(const void* z, const float* scale, const float* shift, void* y, void* u, int B, int H, int W, int C, int dtype,
+                               void* stream) {
+  const int vec = dtype == KSMI_BF16 ? 8 : 4;
+  if (C < vec || C % vec || B < 1 || H < 1 || W < 1) return ksmi_fail(KSMI_E_ARG, "affine_relu_upsample2: C must be a multiple of the vector, B, H, W >= 1");
+  if (!z || !scale || !shift || !y || !u) return ksmi_fail(KSMI_E_ARG, "affine_relu_upsample2: null argument");
+  const int64_t n = (int64_t)B * H * W * (C / vec);
+  KSMI_DT(dtype,
+          hipLaunchKernelGGL(affine_relu_upsample2_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)z, scale, shift, (bf16_t*)y, (bf16_t*)u, B, H, W, C),
+          hipLaunchKernelGGL(affine_relu_upsample2_kernel<float>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)z, scale, shift, (float*)y, (float*)u, B, H, W, C));
+  return ksmi_check_launch("affine_relu_upsample2");
 }
 
 }  // extern "C"

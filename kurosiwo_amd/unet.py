@@ -20,9 +20,8 @@ LAYERS = ((64, 1), (128, 2), (256, 2), (512, 2))
 DECODER_CHANNELS = (256, 128, 64, 32, 16)
 
 
-def unet_specs(in_channels, classes):
-    p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
-    bn = functools.partial(bn_spec, p, b, c)
+def encoder_specs(p, bn, in_channels):
+    """the torchvision ResNet-18 encoder entries (shared with unetpp.unetpp_specs)"""
     p["encoder.conv1.weight"] = (64, in_channels, 7, 7)
     bn("encoder.bn1", 64)
     cin = 64
@@ -37,6 +36,12 @@ def unet_specs(in_channels, classes):
                 p[f"{k}.downsample.0.weight"] = (ch, cin, 1, 1)
                 bn(f"{k}.downsample.1", ch)
             cin = ch
+
+
+def unet_specs(in_channels, classes):
+    p, b, c = OrderedDict(), OrderedDict(), OrderedDict()
+    bn = functools.partial(bn_spec, p, b, c)
+    encoder_specs(p, bn, in_channels)
     enc = (512, 256, 128, 64, 64)
     ins = (enc[0],) + DECODER_CHANNELS[:-1]
     skips = enc[1:] + (0,)
@@ -64,6 +69,9 @@ class Unet(ArenaModule):
         self.in_channels, self.classes, self.precision = in_channels, classes, precision
         ps, bs, cs = unet_specs(in_channels, classes)
         self._setup_arena(ps, bs, cs)
+        self._init_weights()
+
+    def _init_weights(self):
         with torch.no_grad():
             for key, shp in self._pspec.items():
                 p = self._p(key).view(shp)

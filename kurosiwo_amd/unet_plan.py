@@ -160,22 +160,32 @@ class UnetPlan(ResNetPlan):
         self._build_lists(self._build_unet)
 
     # ---------------------------------------------------------------- DecoderBlock (smp unet/decoder.py)
-    def _decoder_block(self, k, xd, Cin, skip, Cs, Cout, h, w):
+    def _decoder_block(self, k, xd, Cin, skips, Cout, h, w, U=None, up_out=False, multi_writer=False):
+        """y = conv3x3-BN-ReLU twice over cat(nearest x2 of xd, *skips); skips = [(tensor, channels), ...] at 2h x 2w, in concat order.
+        U: the upsampled xd when its producer already wrote it (up_out of that block).  up_out: y feeds a next block as its upsampled
+        input, so the BatchNorm apply also writes the x2 copy (self._up[id(y)], ksmi_affine_relu_upsample2).  multi_writer: d(xd) may
+        have earlier writers (UNet++: xd is also somebody's skip), so its upsample backward takes the accumulate flag."""
         B, dt = self.B, self.dt
         H2, W2 = 2 * h, 2 * w
         npix = B * H2 * W2
-        U = self.buf(B, H2, W2, Cin)
-        self.fwd.add("ksmi_upsample2_forward", lambda: (xd.data_ptr(), U.data_ptr(), B, h, w, Cin, 0, dt), self._elt_meta("upsample2", 5 * B * h * w * Cin))
+        if U is None:
+            U = self.buf(B, H2, W2, Cin)
+            self.fwd.add("ksmi_upsample2_forward", lambda: (xd.data_ptr(), U.data_ptr(), B, h, w, Cin, 0, dt), self._elt_meta("upsample2", 5 * B * h * w * Cin))
         z1, z2, y = self.buf(B, H2, W2, Cout), self.buf(B, H2, W2, Cout), self.buf(B, H2, W2, Cout)
         svA, svB = _Saved(max(Cout, 16), self.dev), _Saved(max(Cout, 16), self.dev)
-        srcs = [SrcSpec(U, Cin)] + ([SrcSpec(skip, Cs)] if skip is not None else [])
-        Kt = Cin + (Cs if skip is not None else 0)
+        srcs = [SrcSpec(U, Cin)] + [SrcSpec(t, cs) for t, cs in skips]
+        Kt = Cin + sum(cs for _, cs in skips)
         rows, cpad = self._cv(self.fwd, f"{k}.conv1", srcs, [(z1, Cout, 0, 0, Cout, 0)], f"{k}.conv1.0.weight", H2, W2, H2, W2, 3, 1, 1, Cout, Kt, stats=self.training)
         self._bn_finalize(f"{k}.conv1.1", svA, rows, cpad, Cout, npix)
         a1 = [SrcSpec(z1, Cout, scale=svA.scale_t, shift=svA.shift_t, relu=1)]
         rows, cpad = self._cv(self.fwd, f"{k}.conv2", a1, [(z2, Cout, 0, 0, Cout, 0)], f"{k}.conv2.0.weight", H2, W2, H2, W2, 3, 1, 1, Cout, Cout, stats=self.training)
         self._bn_finalize(f"{k}.conv2.1", svB, rows, cpad, Cout, npix)
-        self._affine(self.fwd, z2, svB, y, npix, Cout, 1)
+        if up_out:
+            Uy = self._up[id(y)] = self.buf(B, 2 * H2, 2 * W2, Cout)
+            self.fwd.add("ksmi_affine_relu_upsample2", lambda: (z2.data_ptr(), svB.scale, svB.shift, y.data_ptr(), Uy.data_ptr(), B, H2, W2, Cout, dt),
+                         self._elt_meta("bn_apply_up2", 6 * npix * Cout))
+        else:
+            self._affine(self.fwd, z2, svB, y, npix, Cout, 1)
 
         def bwd():
             dy = self.gbuf(y)
@@ -186,20 +196,26 @@ class UnetPlan(ResNetPlan):
                                  mask=self._bnmask(z1, svA), stats=True, dgrad=True)
             self._bn_backward(f"{k}.conv1.1", da1, z1, svA, dz1, r2, c2, Cout, npix, npix, 0)
             self._wg(srcs, dz1, Cout, f"{k}.conv1.0.weight", H2, W2, H2, W2, 3, 1, 1, Kt)
-            dsts = [(dU, Cin, 0, 0, Cin, 0)]
-            if skip is not None:
-                dsts.append((self.gbuf(skip), Cs, 0, Cin, Cs, self.gacc(skip)))
+            dsts, off = [(dU, Cin, 0, 0, Cin, 0)], Cin
+            for t, cs in skips:
+                dsts.append((self.gbuf(t), cs, 0, off, cs, self.gacc(t)))
+                off += cs
             self._conv3(self.bwd, f"{k}.conv1", [SrcSpec(dz1, Cout)], dsts, f"{k}.conv1.0.weight", None, B, H2, W2, Kt, Cout, dgrad=True)
             dxd = self.gbuf(xd)
-            if self.gacc(xd):
+            acc = self.gacc(xd)
+            if multi_writer:
+                self.bwd.add("ksmi_upsample2_backward_acc", lambda: (dU.data_ptr(), None, dxd.data_ptr(), acc, B, h, w, Cin, 0, dt),
+                             self._elt_meta("upsample2_bwd", (5 + acc) * B * h * w * Cin))
+                return
+            if acc:
                 raise _lib.KsmiError("unexpected second writer of a decoder input gradient")
             self.bwd.add("ksmi_upsample2_backward", lambda: (dU.data_ptr(), None, dxd.data_ptr(), B, h, w, Cin, 0, dt), self._elt_meta("upsample2_bwd", 5 * B * h * w * Cin))
         self._bwd.append(bwd)
         return y
 
     # ---------------------------------------------------------------- the graph
-    def _build_unet(self):
-        B, H, W, dt = self.B, self.H, self.W, self.dt
+    def _build_encoder(self):
+        """stem and layer1..4 -> ([f1..f5], height, width of f5)"""
         f1, p, H2, W2 = self._resnet_stem("encoder", self.x)
         feats = [f1]
         t, cin, h, w = p, 64, H2, W2
@@ -210,16 +226,11 @@ class UnetPlan(ResNetPlan):
                 h, w, cin = h // s_, w // s_, ch
             feats.append(t)
         self.named.update({f"f{i + 1}": f for i, f in enumerate(feats)})
-        skips = feats[::-1]                      # f5, f4, f3, f2, f1
-        chans = (512, 256, 128, 64, 64)
-        y, cy = skips[0], 512
-        for i, co in enumerate(DECODER_CHANNELS):
-            skip = skips[i + 1] if i + 1 < len(skips) else None
-            cs = chans[i + 1] if skip is not None else 0
-            y = self._decoder_block(f"decoder.blocks.{i}", y, cy, skip, cs, co, h, w)
-            self.named[f"d{i}"] = y
-            h, w, cy = 2 * h, 2 * w, co
-        # segmentation head
+        return feats, h, w
+
+    def _build_head(self, y):
+        """segmentation head: conv3x3(16 -> classes) + bias on the last decoder output"""
+        B, H, W, dt = self.B, self.H, self.W, self.dt
         P = self.buf(B, H, W, CS)
         nc = self.nc
         self._cv(self.fwd, "segmentation_head", [SrcSpec(y, 16)], [(P, CS, 0, 0, nc, 0)], "segmentation_head.0.weight", H, W, H, W, 3, 1, 1, nc, 16,
@@ -228,6 +239,46 @@ class UnetPlan(ResNetPlan):
         self.fwd.add("ksmi_out_to_nchw", lambda: (P.data_ptr(), self.logits.data_ptr(), B, nc, CS, HW, 0, dt))
         self._bwd.append(lambda: self._class_head_bwd("segmentation_head", "segmentation_head.0.weight", "segmentation_head.0.bias", y, 16))
 
+    def _build_unet(self):
+        feats, h, w = self._build_encoder()
+        skips = feats[::-1]                      # f5, f4, f3, f2, f1
+        chans = (512, 256, 128, 64, 64)
+        y, cy = skips[0], 512
+        for i, co in enumerate(DECODER_CHANNELS):
+            skip = [(skips[i + 1], chans[i + 1])] if i + 1 < len(skips) else []
+            y = self._decoder_block(f"decoder.blocks.{i}", y, cy, skip, co, h, w)
+            self.named[f"d{i}"] = y
+            h, w, cy = 2 * h, 2 * w, co
+        self._build_head(y)
+
     # ---------------------------------------------------------------- execution
     def run_forward(self, x):
         return self._run_forward(self.logits, (x, self.x))
+
+
+class UnetPlusPlusPlan(UnetPlan):
+    """smp UnetPlusPlusDecoder on the same pieces (unetpp.py: the block table and the forward order): eleven DecoderBlocks on a dense grid.
+    Every feature map has several gradient writers ("=" by the first, "+=" by the later ones, through gacc): the blocks are built in
+    forward order, so the reversed closure list runs every consumer of a tensor before its producer.  A block output that is the next
+    block's upsampled input gets its x2 copy from the BatchNorm apply pass (KSMI_UNETPP_FUSED_UP=0: the two-launch pair, for the A/B)."""
+
+    def _build_unet(self):
+        from .unetpp import block_table, forward_order
+        fused = os.environ.get("KSMI_UNETPP_FUSED_UP", "1") != "0"
+        self._up = {}
+        feats, h5, w5 = self._build_encoder()
+        features = feats[::-1]                   # f5, f4, f3, f2, f1
+        table, x = block_table(), {}
+        for name in forward_order():
+            d, l = (int(v) for v in name.split("_")[1:])
+            ci, cs, co = table[name]
+            xd = features[d] if l == d else x[(d, l - 1)]
+            skips = [(x[(i, l)], table[f"x_{i}_{l}"][2]) for i in range(d + 1, l + 1)] if l < 4 else []
+            if l < 4:
+                skips.append((features[l + 1], cs // (l + 1 - d)))
+            assert ci == xd.shape[-1] and cs == sum(c for _, c in skips) and all(t.shape[-1] == c for t, c in skips), name
+            up_out = fused and (l < 3 or name == "x_0_3")        # x_d_l is the upsampled input of x_d_{l+1}
+            y = self._decoder_block(f"decoder.blocks.{name}", xd, ci, skips, co, h5 << l, w5 << l, U=self._up.get(id(xd)), up_out=up_out,
+                                    multi_writer=True)
+            x[(d, l)] = self.named[name] = y
+        self._build_head(x[(0, 4)])

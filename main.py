@@ -5,6 +5,7 @@ for the tasks/methods that have a HIP implementation: task "cd" method "snunet",
 
   python main.py --method snunet --inputs pre_event_1 post_event [--dem] [--slope] [--batch_size N] [--seed S]
   python main.py --method finetune --inputs pre_event_1 pre_event_2 post_event [--batch_size N]
+  python main.py --method unet | unetplusplus --inputs post_event [--batch_size N]
   python main.py --method mae [--batch_size N]        (MAE pre-training of the FloodViT encoder)
 """
 import argparse

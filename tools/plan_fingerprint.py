@@ -136,6 +136,10 @@ def models(family, precision):
         from kurosiwo_amd.bitcd import define_G
         for net_g in ("base_resnet18", "base_transformer_pos_s4", "base_transformer_pos_s4_dd8_dedim8"):
             yield f"bit-cd {net_g} B2", define_G({"net_G": net_g}, 2, precision=precision), (2, H, W, True, True), (2, H, W, False, False)
+    elif family == "unetplusplus":
+        from kurosiwo_amd.unetpp import UnetPlusPlus
+        yield ("unetplusplus B2", UnetPlusPlus("resnet18", encoder_weights=None, in_channels=2, classes=3, precision=precision),
+               (2, H, W, True, True), (2, H, W, False, False))
     elif family == "floodvit":
         from kurosiwo_amd.floodvit import FinetunerSegmentation, ViT
         enc = ViT(image_size=224, patch_size=16, num_classes=1000, dim=1024, depth=24, heads=16, mlp_dim=2048, channels=6)
@@ -150,7 +154,7 @@ def models(family, precision):
 
 
 # (new families are appended: the dump of the earlier names, and its hash in LABNOTES, stays comparable across commits)
-FAMILIES = ("snunet", "changeformer", "unet", "siam-conc", "bit-cd", "floodvit", "mae", "siam-diff", "bit-cd-variants")
+FAMILIES = ("snunet", "changeformer", "unet", "siam-conc", "bit-cd", "floodvit", "mae", "siam-diff", "bit-cd-variants", "unetplusplus")
 
 
 def arena_models(family):
