@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define KSMI_ABI_VERSION 7   /* 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list; later, backward-compatible: the dice / Lovasz / focal losses ksmi_seg_loss_workspace, _forward, _backward); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
+#define KSMI_ABI_VERSION 8   /* 8: the stream-ordering state of a step has one owner (ksmi_runner_order, _fork_side, _mark_side, _wait_side); 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list; later, backward-compatible: the dice / Lovasz / focal losses ksmi_seg_loss_workspace, _forward, _backward); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
 #define KSMI_F32 0
 #define KSMI_BF16 1
 #define KSMI_E_ARG (-1)
@@ -54,8 +54,12 @@ int ksmi_chunk_elems(int dtype);
  *     slots (integers / pointers by value, float in the low 32 bits, double by bit pattern).  lane 0 | 1 = compute lane; side 1 | 2 =
  *     the launch goes to that weight-gradient stream behind an event recorded on its lane's stream; tag >= 0 = record an event
  *     behind it that KSMI_OP_WAIT_SIDE(tag) consumes.
- *   ORDER: lane b waits for everything lane a was handed.  WAIT_SIDE: lane waits for the tagged side launch (tag < 0: the whole side stream).
- * `skip` (or NULL): one byte per op, non-zero = leave that CALL out this time.  On failure *failed_at = index of the op. */
+ *   ORDER: lane b waits for everything lane a was handed.  WAIT_SIDE: the entry's lane and the lane of the last launch wait for the
+ *     tagged side launch (tag < 0: the whole side stream, if it was handed work; a tag never recorded: nothing).
+ * `skip` (or NULL): one byte per op, non-zero = leave that CALL out this time.  On failure *failed_at = index of the op.
+ * The runner is the ONE owner of a step's cross-stream state (fork events, tagged events, busy / dirty flags): a walk of the list in the
+ * host language (timed runs, hooks on every entry, collectives between launches) makes its launches itself and takes the same four
+ * transitions from ksmi_runner_order / _fork_side / _mark_side / _wait_side (ABI 8), so lists of one step may be walked either way. */
 #define KSMI_OP_CALL 0
 #define KSMI_OP_ORDER 1
 #define KSMI_OP_WAIT_SIDE 2
@@ -70,6 +74,15 @@ int ksmi_runner_destroy(void* runner);
 /* lane1 NULL: one compute lane; side NULL: weight gradients stay on their lane's stream */
 int ksmi_runner_set_streams(void* runner, void* main_stream, void* lane1, void* side, void* side2);
 int ksmi_run_list(void* runner, const ksmi_op* ops, int first, int last, const uint8_t* skip, int32_t* failed_at);
+/* the four transitions ksmi_run_list makes, one at a time.  Without a second lane / a side stream they do nothing and return 0
+ * (fork_side then hands back the lane's stream); a NULL runner is KSMI_E_ARG.
+ *   order: dst_lane waits for everything src_lane was handed.  fork_side: side stream side_ix (0 | 1) waits for what `lane` was handed;
+ *   *stream_out = the stream the launch goes to.  mark_side: record the event of `tag` behind that launch.  wait_side: as WAIT_SIDE
+ *   above, lane = the entry's lane, cur_lane = the lane of the walk's last launch. */
+int ksmi_runner_order(void* runner, int src_lane, int dst_lane);
+int ksmi_runner_fork_side(void* runner, int lane, int side_ix, void** stream_out);
+int ksmi_runner_mark_side(void* runner, int tag, int side_ix);
+int ksmi_runner_wait_side(void* runner, int lane, int cur_lane, int tag);
 /* end of a step: main waits for every other stream that was handed work; tagged events are forgotten */
 int ksmi_runner_join(void* runner);
 

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libksmi.so")
 KSMI_F32, KSMI_BF16 = 0, 1
 LOSS_DICE, LOSS_LOVASZ, LOSS_FOCAL = 1, 2, 3          # KSMI_LOSS_* (ksmi_seg_loss_*)
 MAX_SRC, MAX_CHUNKS = 6, 72
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class KsmiError(RuntimeError):
@@ -107,6 +107,10 @@ SIGNATURES = {
     "ksmi_runner_destroy": (_i, [_vp]),
     "ksmi_runner_set_streams": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ksmi_run_list": (_i, [_vp, _vp, _i, _i, _vp, C.POINTER(C.c_int32)]),
+    "ksmi_runner_order": (_i, [_vp, _i, _i]),
+    "ksmi_runner_fork_side": (_i, [_vp, _i, _i, C.POINTER(C.c_void_p)]),
+    "ksmi_runner_mark_side": (_i, [_vp, _i, _i]),
+    "ksmi_runner_wait_side": (_i, [_vp, _i, _i, _i]),
     "ksmi_runner_join": (_i, [_vp]),
     "ksmi_conv_dispatch_info": (_i, [C.POINTER(ConvDesc), _i, C.POINTER(C.c_int32)]),
     "ksmi_chunk_elems": (_i, [_i]),

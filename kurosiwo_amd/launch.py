@@ -105,7 +105,8 @@ class LaunchList:
     # ---- compiled form (round 6): the list as an array of ksmi_op walked by ONE C-ABI call per segment (csrc/runlist.hip) instead of one
     # ctypes call + stream switch + up to three torch event calls per launch in Python (host_issue_ms_per_step: 9 ms of a 14 ms SNUNet
     # step, 29 of 34 ms for ChangeFormer).  The Python walk below stays for timed runs (a kernel timer brackets single launches), for hooks
-    # without an index list, for SyncBN's collectives, and as the cross-check (KSMI_RUN_LIST=0; tests/test_gpu_graph.py).
+    # without an index list, for SyncBN's collectives, and as the cross-check (KSMI_RUN_LIST=0; tests/test_gpu_graph.py).  Both walks take
+    # every cross-stream edge from the step's one runner (StepStreams.runner), so the lists of one step may mix them.
     fast = os.environ.get("KSMI_RUN_LIST", "1") != "0"
     _compiled = None
 
@@ -115,12 +116,10 @@ class LaunchList:
         n = len(self.calls)
         ops = (_lib.Op * max(n, 1))()
         slots, where, skips, names, ok = [], [], [], [], True
-        lane1 = side = False               # does the list hand work to lane 1 / to a side stream (StepStreams.claim)?
         for i, (fn, args, name, meta) in enumerate(self.calls):
             op = ops[i]
             op.tag, op.sig = -1, -1
             op.lane = int(meta.get("lane", 0))
-            lane1 |= op.lane != 0 or name == "@wait"
             names.append(name)
             if fn is None:
                 if name == "@wait":
@@ -143,7 +142,6 @@ class LaunchList:
             op.side = (2 if meta.get("side_ix", 0) else 1) if meta.get("side") else 0
             if op.side and meta.get("side_tag") is not None:
                 op.tag = _tag_id(meta["side_tag"])
-            side |= bool(op.side)
             where.append((i, len(slots)))
             slots += [_slot(c, v, struct) for c, v in zip(codes, args)]
             if meta.get("skip_if") is not None:
@@ -152,7 +150,7 @@ class LaunchList:
         base = C.addressof(arr)
         for i, off in where:
             ops[i].args = base + 8 * off
-        self._compiled = {"ops": ops, "slots": arr, "n": n, "skips": skips, "names": names, "ok": ok, "failed": C.c_int32(-1), "lane1": lane1, "side": side,
+        self._compiled = {"ops": ops, "slots": arr, "n": n, "skips": skips, "names": names, "ok": ok, "failed": C.c_int32(-1),
                           "skipbuf": (C.c_uint8 * max(n, 1))() if skips else None}
         return self._compiled
 
@@ -161,8 +159,6 @@ class LaunchList:
         lib = _lib.load()
         if streams is not None:
             streams.begin()
-            if (cp["lane1"] and streams.lanes) or (cp["side"] and streams.use_side):
-                streams.claim("compiled")
             runner = streams.runner()
         else:
             runner = _plain_runner(stream_ptr())
@@ -190,8 +186,9 @@ class LaunchList:
         "@wait" entries are no-ops).  With streams: launches of lane 1 go to the second compute stream, launches tagged "side" (the
         weight gradients: nothing on the critical path of the backward pass reads them) to the side stream behind an event recorded
         on the issuing lane's stream at that point of the list, so that independent work fills the machine next to the
-        bandwidth-bound BatchNorm / elementwise launches of the critical path; the caller joins (StepStreams.join) before
-        anything outside the lists reads the results."""
+        bandwidth-bound BatchNorm / elementwise launches of the critical path; the caller joins (StepStreams.join / end) before
+        anything outside the lists reads the results.  The walk below makes the launches and the stream switches; the forks, tagged
+        events and waits are the runner's (StepStreams.order / fork_side / mark_side / wait_side), as in the compiled walk."""
         if (timer is None or not getattr(timer, "active", True)) and self.fast and self.calls and (hook is None or hook_at is not None):
             cp = self._compiled or self._compile()
             if cp["ok"]:
@@ -214,7 +211,7 @@ class LaunchList:
                 if fn is None:
                     if name == "@wait_side":
                         if streams is not None and streams.use_side:
-                            streams.wait_side(args[0])
+                            streams.wait_side(args[0], meta["lane"] if streams.lanes else 0, cur)
                     elif streams is not None and streams.lanes:
                         streams.order(*args)
                     if hook is not None:
@@ -230,10 +227,10 @@ class LaunchList:
                 if timed:
                     timer.begin(meta["kind"], meta)
                 if streams is not None and streams.use_side and not timed and meta.get("side"):     # (a timed launch is bracketed by events on its lane's stream)
-                    six = meta.get("side_ix", 0)
-                    rc = fn(*args, streams.fork_side(six) if six else streams.fork_side())
-                    if meta.get("side_tag") is not None:
-                        streams.mark_side(meta["side_tag"], six) if six else streams.mark_side(meta["side_tag"])
+                    six = 1 if meta.get("side_ix", 0) else 0
+                    rc = fn(*args, streams.fork_side(lane, six))
+                    if rc == 0 and meta.get("side_tag") is not None:
+                        streams.mark_side(meta["side_tag"], six)
                 else:
                     rc = fn(*args, st)
                 if timed:
@@ -250,7 +247,9 @@ class LaunchList:
 class StepStreams:
     """The HIP streams of one train step: main = the caller's current stream (lane 0), lane1 = a second compute lane for the
     deeper decoder blocks (SNUNetPlan: they depend on the level-0 blocks only through the Up1_j edges), side = the weight gradients.
-    Cross-stream ordering is plain event record / wait pairs, so a step that uses them still captures into one HIP graph."""
+    Cross-stream ordering is plain event record / wait pairs, so a step that uses them still captures into one HIP graph.  The
+    ordering state (fork events, tagged events, busy / dirty flags) lives in ONE place, the runner of csrc/runlist.hip: the compiled
+    walk drives it from C, the Python walk through order / fork_side / mark_side / wait_side below."""
 
     def __init__(self, device, lanes=True, side=True):
         self.side = torch.cuda.Stream(device=device)       # (stream priorities measured no better, DESIGN.md §5)
@@ -263,21 +262,8 @@ class StepStreams:
         self.lanes, self.use_side = bool(lanes), bool(side)
         self.side_ptr = C.c_void_p(self.side.cuda_stream)
         self.main = None
-        self.dirty = False
-        self.side_busy = False
-        self.events = {}           # side_tag -> event recorded behind that launch on the side stream (LaunchList.add_wait_side)
 
     _runner = None
-    _walker = None                 # which walk of LaunchList.run has handed work to lane 1 / a side stream since begin()
-
-    def claim(self, walker):
-        """The fork / tag / busy state of a step lives with the walker that created it (here for the Python walk, in the runner for
-        the compiled one), so a "@wait_side" of one walker would not see a side-stream launch of the other: one walker per step."""
-        if self._walker not in (None, walker):
-            raise _lib.KsmiError(f"launch lists of one step on two walkers: the {self._walker} walk has handed work to lane 1 or a side "
-                                 f"stream of this step, and now the {walker} walk of another list does (between begin() and end() every "
-                                 "multi-stream list runs on the same walker: a timed or SyncBN step takes the Python walk for all of them)")
-        self._walker = walker
 
     def begin(self):
         if self.main is None:
@@ -291,7 +277,7 @@ class StepStreams:
                                             self.side_ptr if self.use_side else None, self.side2_ptr if self.use_side else None)
 
     def runner(self):
-        """executor state of the compiled launch lists (csrc/runlist.hip) bound to this step's streams; call after begin()"""
+        """executor state (csrc/runlist.hip) bound to this step's streams, created at its first use; call after begin()"""
         if self._runner is None:
             self._runner = C.c_void_p(_lib.load().ksmi_runner_create())
             self._bind_runner()
@@ -307,35 +293,21 @@ class StepStreams:
     def stream(self, lane):
         return self.main if lane == 0 else self.lane1
 
-    def _event(self, stream):
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        return ev
-
     def order(self, src, dst):
-        self.claim("Python")
-        self.stream(dst).wait_event(self._event(self.stream(src)))
-        self.dirty = True
+        _lib.check(_lib.load().ksmi_runner_order(self.runner(), src, dst), "ksmi_runner_order")
 
-    def fork_side(self, ix=0):
-        two = ix and self.side2 is not None
-        self.claim("Python")
-        (self.side2 if two else self.side).wait_event(self._event(torch.cuda.current_stream()))
-        self.dirty = self.side_busy = True
-        return self.side2_ptr if two else self.side_ptr
+    def fork_side(self, lane, ix=0):
+        """side stream `ix` waits for what `lane` was handed so far; returns the stream the weight gradient goes to"""
+        out = C.c_void_p()
+        _lib.check(_lib.load().ksmi_runner_fork_side(self.runner(), lane, ix, C.byref(out)), "ksmi_runner_fork_side")
+        return out
 
     def mark_side(self, tag, ix=0):
-        self.events[tag] = self._event(self.side2 if (ix and self.side2 is not None) else self.side)
+        _lib.check(_lib.load().ksmi_runner_mark_side(self.runner(), _tag_id(tag), ix), "ksmi_runner_mark_side")
 
-    def wait_side(self, tag):
-        if tag is None:
-            if self.side_busy:                 # (nothing handed to the side stream since the last such wait: nothing to wait for)
-                torch.cuda.current_stream().wait_stream(self.side)
-                if self.side2 is not None:
-                    torch.cuda.current_stream().wait_stream(self.side2)
-                self.side_busy = False
-        elif tag in self.events:
-            torch.cuda.current_stream().wait_event(self.events.pop(tag))
+    def wait_side(self, tag, lane, cur):
+        """the entry's lane and the lane of the last launch wait for the side launch tagged `tag` (None: for the side streams, if busy)"""
+        _lib.check(_lib.load().ksmi_runner_wait_side(self.runner(), lane, cur, -1 if tag is None else _tag_id(tag)), "ksmi_runner_wait_side")
 
     def all_streams(self):
         """every stream a launch of the step may have run on"""
@@ -343,19 +315,15 @@ class StepStreams:
                             self.side2 if self.use_side else None) if s is not None]
 
     def join(self):
-        """the current stream waits for every other stream of the step, whichever walker handed them their work"""
-        if self.dirty:
-            cur = torch.cuda.current_stream()
-            for s in (self.main, self.lane1, self.side, self.side2):
-                if s is not None and s.cuda_stream != cur.cuda_stream:
-                    cur.wait_stream(s)
-        if self.main is not None and torch.cuda.current_stream().cuda_stream == self.main.cuda_stream:
-            self.dirty = False
-        if self._runner is not None:                 # (the compiled lists keep their own dirty / tag state: main joins the other streams)
+        """main waits for every other stream of the step that was handed work (by either walk), and the caller's current stream, if it
+        is another one, for main"""
+        if self._runner is not None:
             _lib.check(_lib.load().ksmi_runner_join(self._runner), "ksmi_runner_join")
+        if self.main is not None:
+            cur = torch.cuda.current_stream()
+            if cur.cuda_stream != self.main.cuda_stream:
+                cur.wait_stream(self.main)
 
     def end(self):
         self.join()
-        self.main = self._walker = None
-        self.events.clear()
-        self.side_busy = False
+        self.main = None

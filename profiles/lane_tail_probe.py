@@ -15,10 +15,9 @@ lane = st._ss
 orig_join = lane.join
 rec = []
 def join():
-    if lane.dirty:
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(torch.cuda.current_stream()); b.record(lane.side)
-        rec.append((a, b))
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(torch.cuda.current_stream()); b.record(lane.side)
+    rec.append((a, b))
     orig_join()
 lane.join = join
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

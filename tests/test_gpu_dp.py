@@ -401,7 +401,7 @@ def _family_worker(rank, world, port, q, family, precision, wire, mode):
     missing = [k for k in model._poff if k not in step.plan.param_ready]
     covered = sum(e - s for s, e, _ in step.reducer.buckets) == model.flat_params.numel()
     q.put((rank, losses, model.flat_params.detach().cpu().numpy(), covered, missing, len(step.reducer.buckets), step.reducer.hook_indices(),
-           step._ss is not None and step._ss._runner is not None))
+           step._ss is not None and bool(step.plan.bwd._compiled and step.plan.bwd._compiled["ok"])))
     dist.destroy_process_group()
 
 

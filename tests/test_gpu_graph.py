@@ -178,8 +178,69 @@ def test_compiled_launch_list_equals_the_python_walk(family, monkeypatch):
             args = (xA.cuda(), y.cuda()) if family in ("unet", "floodvit") else (xA.cuda(), xB.cuda(), y.cuda())
             losses.append(st.step(*args).clone())
         torch.cuda.synchronize()
-        assert (st.plan.bwd._compiled is not None) == fast and (st._ss._runner is not None) == fast
+        assert (st.plan.bwd._compiled is not None) == fast and st._ss._runner is not None      # (one runner under both walks)
         out.append((losses, m.flat_params.clone(), m.flat_grads.clone()))
     for a, b in zip(out[0][0], out[1][0]):
         assert torch.equal(a, b), (a.tolist(), b.tolist())
     assert torch.equal(out[0][2], out[1][2]) and torch.equal(out[0][1], out[1][1])
+
+
+@pytest.mark.parametrize("family", ["snunet", "floodvit"])
+def test_lists_of_one_step_may_mix_walkers(family):
+    """The fork / tag / busy state of a step has one owner (the runner of csrc/runlist.hip, driven by both walks), so one list of a step
+    may take the Python walk (as a list with SyncBN's collectives or a hook without an index list must) while another runs compiled:
+    forward on one walk and backward on the other give the all-compiled trajectory bit for bit.  snunet: lane hand-overs in the forward
+    list too; floodvit: tagged side-stream gradients."""
+    B, S = (16, 224) if family == "floodvit" else (4, 224)
+    data = _batches(3, B, 2, S, 53)
+    out = []
+    for fwd_fast, bwd_fast in ((True, True), (False, True), (True, False)):
+        m, st = _lane_case(family, B, S, True, False)
+        st.plan.fwd.fast, st.plan.bwd.fast = fwd_fast, bwd_fast
+        losses = []
+        for xA, xB, y in data:
+            args = (xA.cuda(), y.cuda()) if family == "floodvit" else (xA.cuda(), xB.cuda(), y.cuda())
+            losses.append(st.step(*args).clone())
+        torch.cuda.synchronize()
+        assert (st.plan.fwd._compiled is not None) == fwd_fast and (st.plan.bwd._compiled is not None) == bwd_fast
+        assert st._ss is not None and st._ss._runner is not None
+        out.append((losses, m.flat_params.clone(), m.flat_grads.clone()))
+    for got in out[1:]:
+        for a, b in zip(out[0][0], got[0]):
+            assert torch.equal(a, b), (a.tolist(), b.tolist())
+        assert torch.equal(out[0][2], got[2]) and torch.equal(out[0][1], got[1])
+
+
+@pytest.mark.parametrize("wait", ["t", None])
+@pytest.mark.parametrize("producer_fast,consumer_fast", [(False, False), (False, True), (True, False), (True, True)])
+def test_a_tag_recorded_by_one_walker_is_waited_for_by_the_other(producer_fast, consumer_fast, wait):
+    """A side-stream launch made by one walk of LaunchList.run and the "@wait_side" of a list on the other walk meet in the step's one
+    runner: the producer list reads X on the (parked) side stream, the consumer list waits for its tag (or, wait None, for the busy side
+    stream) and then overwrites X on main.  Without the edge the producer would read the overwritten X."""
+    from kurosiwo_amd import _lib, launch as sp
+    from kurosiwo_amd import functional as F
+    dev = torch.device("cuda:0")
+    n = 1 << 20
+    g = torch.Generator().manual_seed(61)
+    X, Z = torch.randn(n, generator=g).to(dev), torch.randn(n, generator=g).to(dev)
+    G = torch.zeros(n, device=dev)
+    want_g, want_x = F.gelu(X), F.gelu(Z)                  # single stream
+    torch.cuda.synchronize()
+    lib, f32 = _lib.load(), _lib.KSMI_F32
+    producer, consumer = sp.LaunchList(), sp.LaunchList()
+    producer.add("ksmi_gelu_forward", lambda: (X.data_ptr(), G.data_ptr(), n, f32), {"kind": "gelu", "bytes": 0, "flops": 0, "side": True, "side_tag": "t"})
+    consumer.add_wait_side(wait)
+    consumer.add("ksmi_gelu_forward", lambda: (Z.data_ptr(), X.data_ptr(), n, f32), {"kind": "gelu", "bytes": 0, "flops": 0})
+    producer.resolve(lib)
+    consumer.resolve(lib)
+    producer.fast, consumer.fast = producer_fast, consumer_fast
+    ss = sp.StepStreams(dev, lanes=False, side=True)
+    with torch.cuda.stream(ss.side):
+        torch.cuda._sleep(25_000_000)                      # park the side stream: main runs as far ahead as its waits allow
+    producer.run(None, None, ss)
+    consumer.run(None, None, ss)
+    ss.end()
+    torch.cuda.synchronize()
+    assert (producer._compiled is not None) == producer_fast and (consumer._compiled is not None) == consumer_fast
+    assert torch.equal(G, want_g)
+    assert torch.equal(X, want_x)

@@ -166,7 +166,7 @@ def test_compiled_launch_list_equals_the_python_walk(monkeypatch):
         st = _train_step(m, Bq, S, overlap_wgrad=True, overlap_lanes=True, graph=False)
         losses = [st.step(x.cuda(), y.cuda()).clone() for x, y in data]
         torch.cuda.synchronize()
-        assert (st.plan.bwd._compiled is not None) == fast and (st._ss._runner is not None) == fast
+        assert (st.plan.bwd._compiled is not None) == fast and st._ss._runner is not None      # (one runner under both walks)
         names = [c[2] for c in st.plan.fwd.calls + st.plan.bwd.calls]
         assert "ksmi_upsample2_backward_acc" in names and "ksmi_affine_relu_upsample2" in names
         out.append((losses, m.flat_params.clone(), m.flat_grads.clone()))

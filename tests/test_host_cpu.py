@@ -191,14 +191,14 @@ def test_launch_list_orders_side_stream_gradients_behind_tagged_waits(monkeypatc
         def begin(self):
             self.ops.append("begin")
 
-        def fork_side(self):
+        def fork_side(self, lane, ix=0):
             self.ops.append("fork")
             return "SIDE"
 
-        def mark_side(self, tag):
+        def mark_side(self, tag, ix=0):
             self.ops.append(("mark", tag))
 
-        def wait_side(self, tag):
+        def wait_side(self, tag, lane, cur):
             self.ops.append(("wait", tag))
 
     hooked = []
@@ -218,77 +218,27 @@ class _FakeStream:
     def __init__(self, name, log, handle):
         self.name, self.log, self.cuda_stream = name, log, handle
 
-    def wait_event(self, ev):
-        self.log.append((self.name, "wait_event", ev))
-
     def wait_stream(self, s):
         self.log.append((self.name, "wait_stream", s.name))
 
 
 def _step_streams_without_a_gpu(monkeypatch, log):
-    """a launch.StepStreams (side stream on, one compute lane) whose streams and events are recorders; the executor state of a compiled
-    list is bound to null streams, so nothing of HIP is touched"""
+    """a launch.StepStreams (side stream on, one compute lane) whose streams are recorders; its runner is bound to null streams, so
+    nothing of HIP is touched"""
     import ctypes as C
     from kurosiwo_amd import launch as sp
     monkeypatch.setattr(sp, "stream_ptr", lambda: "MAIN")
     main = _FakeStream("main", log, 0)
     monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: main)
-    monkeypatch.setattr(sp.StepStreams, "_event", lambda self, stream: ("event", stream.name))
     ss = object.__new__(sp.StepStreams)
     ss.side, ss.side2, ss.lane1, ss.side_ptr, ss.side2_ptr = _FakeStream("side", log, 1), None, None, C.c_void_p(None), None
-    ss.lanes, ss.use_side, ss.main, ss.dirty, ss.side_busy, ss.events = False, True, None, False, False, {}
+    ss.lanes, ss.use_side, ss.main = False, True, None
     return sp, ss
 
 
-def test_one_step_streams_refuses_a_second_walker(monkeypatch):
-    """launch.StepStreams between begin() and end(): the walker (Python / compiled) that handed work to a side stream owns the
-    step's fork / tag state; a multi-stream list on the other walker raises instead of silently skipping a "@wait_side".
-    Single-stream lists (streams=None) and lists without side-stream work are not part of it, and end() frees the step."""
-    import ctypes as C
-    from kurosiwo_amd import _lib
-    log, calls = [], []
-    sp, ss = _step_streams_without_a_gpu(monkeypatch, log)
-
-    class Lib:
-        def ksmi_w(self, x, st):
-            calls.append((x, st))
-            return 0
-
-    py = sp.LaunchList()                               # a stubbed library: the Python walk
-    py.add("ksmi_w", lambda: (1,), {"kind": "wgrad", "bytes": 0, "flops": 0, "side": True, "side_tag": "t"})
-    py.add_wait_side("t")
-    py.resolve(Lib())
-    d = _lib.ConvDesc()
-    compiled = sp.LaunchList()                         # real entry points: the compiled walk (never reached: the claim comes first)
-    compiled.add("ksmi_conv_wgrad", lambda: (C.byref(d), 1), {"kind": "wgrad", "bytes": 0, "flops": 0, "side": True, "side_tag": "u"})
-    compiled.resolve(_lib.load())
-    plain = sp.LaunchList()                            # nothing for lane 1 or a side stream in it
-    plain.add_wait_side(None)
-    plain.resolve(_lib.load())
-
-    py.run(None, None, ss)
-    assert calls == [(1, ss.side_ptr)] and ss._walker == "Python"
-    assert ("main", "wait_event", ("event", "side")) in log          # the tagged wait saw the Python walk's own mark
-    with pytest.raises(_lib.KsmiError, match="Python walk.*compiled walk"):
-        compiled.run(None, None, ss)
-    plain.run(None, None, ss)                          # compiled, but claims nothing
-    assert plain._compiled is not None and ss._walker == "Python"
-    ss.end()
-    assert ss._walker is None and ss.main is None
-    # the other order: a compiled list first (its claim as LaunchList._run_fast places it), then the Python walk
-    ss.begin()
-    ss.claim("compiled")
-    with pytest.raises(_lib.KsmiError, match="compiled walk.*Python walk"):
-        py.run(None, None, ss)
-    assert len(calls) == 1
-    ss.end()
-    py.run(None, None, ss)                             # a new step: free again
-    assert len(calls) == 2
-
-
 def test_step_streams_join_reaches_the_runner(monkeypatch):
-    """StepStreams.join() joins both halves of a step's stream state: the Python walk's (wait_stream on every other stream) and the
-    compiled walk's (ksmi_runner_join); end() = join() + reset"""
+    """StepStreams.join() is ksmi_runner_join exactly when a runner exists (the step's stream state has one owner), and a current
+    stream other than main then waits for main; end() = join() + reset"""
     from kurosiwo_amd import _lib
     log, joined = [], []
     sp, ss = _step_streams_without_a_gpu(monkeypatch, log)
@@ -296,15 +246,20 @@ def test_step_streams_join_reaches_the_runner(monkeypatch):
     real = lib.ksmi_runner_join
     monkeypatch.setattr(lib, "ksmi_runner_join", lambda r: joined.append(r.value) or real(r))
     ss.join()
-    assert joined == []                                # no compiled list ran on these streams: no runner
+    assert joined == [] and log == []                  # nothing ran on these streams: no runner, nothing to wait for
     ss.begin()
     r = ss.runner()
     assert r.value and ss._runner is r
-    ss.dirty = True
     ss.join()
-    assert joined == [r.value] and ("main", "wait_stream", "side") in log and not ss.dirty
+    assert joined == [r.value] and log == []           # the caller is on main: the runner's join is all of it
+    other = _FakeStream("other", log, 2)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device=None: other)
+    ss.join()
+    assert joined == [r.value, r.value] and log == [("other", "wait_stream", "main")]
     ss.end()
-    assert joined == [r.value, r.value] and ss.main is None
+    assert joined == [r.value] * 3 and log == [("other", "wait_stream", "main")] * 2 and ss.main is None
+    ss.join()                                          # between steps: the runner's (empty) join, no stream to wait for
+    assert joined == [r.value] * 4 and len(log) == 2
 
 
 def test_mirror_freshness_and_skip_if_without_a_gpu(monkeypatch):

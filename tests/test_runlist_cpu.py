@@ -54,6 +54,17 @@ def test_runner_lifecycle_and_argument_checks_without_a_gpu():
     failed = C.c_int32(7)
     assert lib.ksmi_run_list(r, ops, 0, 0, None, C.byref(failed)) == 0 and failed.value == -1        # an empty segment touches nothing
     assert lib.ksmi_run_list(None, ops, 0, 0, None, None) != 0
+    # the four transitions of the Python walk: without a second lane / a side stream they do nothing (and touch nothing of HIP)
+    out = C.c_void_p(5)
+    assert lib.ksmi_runner_order(r, 1, 0) == 0
+    assert lib.ksmi_runner_fork_side(r, 0, 0, C.byref(out)) == 0 and out.value is None           # the (null) main stream
+    out = C.c_void_p(5)
+    assert lib.ksmi_runner_fork_side(r, 1, 1, C.byref(out)) == 0 and out.value is None
+    assert lib.ksmi_runner_mark_side(r, 3, 0) == 0
+    assert lib.ksmi_runner_wait_side(r, 0, 0, 3) == 0 and lib.ksmi_runner_wait_side(r, 0, 0, -1) == 0
+    assert lib.ksmi_runner_join(r) == 0
+    assert lib.ksmi_runner_order(None, 1, 0) != 0 and lib.ksmi_runner_fork_side(None, 0, 0, C.byref(out)) != 0
+    assert lib.ksmi_runner_mark_side(None, 3, 0) != 0 and lib.ksmi_runner_wait_side(None, 0, 0, 3) != 0
     assert lib.ksmi_runner_destroy(r) == 0
 
 

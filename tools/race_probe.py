@@ -1,12 +1,16 @@
 """Repeat the single-stream vs side-stream comparison of a token train step: python tools/race_probe.py mae|floodvit|changeformer [repeats] [delay] [nowait]
 delay: every step first parks the side stream behind a ~10 ms spin kernel and every side-stream launch behind a ~150 us one, so the
 main stream runs as far ahead of each weight gradient as its waits allow -- a missing wait then shows up as a different trajectory
-instead of depending on launch timing."""
+instead of depending on launch timing.  The parking wraps StepStreams.fork_side, which only the Python walk of the launch lists
+calls, so the probe runs every list on that walk (LaunchList.fast = False); the ordering state it exercises is the runner's either way."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import torch
+
+from kurosiwo_amd.launch import LaunchList
+LaunchList.fast = False
 
 fam, reps = sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 6
 delay = len(sys.argv) > 3
@@ -20,14 +24,14 @@ def stepper(st):
             # every launch handed to the side stream first spins ~150 us there (and the whole stream ~10 ms at the start of a step)
             fork = ss.fork_side
 
-            def slow_fork():
-                ptr = fork()
+            def slow_fork(lane, ix=0):
+                ptr = fork(lane, ix)
                 with torch.cuda.stream(ss.side):
                     torch.cuda._sleep(350_000)
                 return ptr
             ss.fork_side, ss._slow = slow_fork, True
             if nowait:
-                ss.wait_side = lambda tag: None
+                ss.wait_side = lambda tag, lane, cur: None
         if delay and ss is not None:
             with torch.cuda.stream(ss.side):
                 torch.cuda._sleep(25_000_000)
