@@ -9,6 +9,7 @@ kurosiwo_amd/dp.py; 1/W folded into the optimiser kernel), and evaluates its sha
 matrices and loss sums are all-reduced, so every rank returns the same metrics; only rank 0 prints and writes checkpoints.
 BatchNorm statistics stay per rank (the reference has no SyncBN): results equal a single-GPU run at batch B/W per BN call.
 """
+import gc
 import os
 
 import torch
@@ -144,6 +145,15 @@ def set_loader_epoch(loader, epoch):
     bs = getattr(loader, "batch_sampler", None)
     if isinstance(bs, RankShardBatchSampler):
         bs.set_epoch(epoch)
+
+
+def before_fork(loader):
+    """`for batch in before_fork(loader)`: a loader with worker processes forks them when iteration starts, and a worker that collects
+    inherited garbage runs its finalisers (captured graphs, events, the launch-list runner) against a HIP runtime that does not survive
+    a fork.  Collect it here, in the process that owns it."""
+    if getattr(loader, "num_workers", 0) > 0:
+        gc.collect()
+    return loader
 
 
 def sharded_collate(samples):

@@ -263,7 +263,9 @@ class StepStreams:
         self.side_ptr = C.c_void_p(self.side.cuda_stream)
         self.main = None
 
+    # (class attributes: an object that never asked for a runner carries neither, and __del__ may run on one that __init__ never finished)
     _runner = None
+    _runner_pid = None      # the process that created the runner: only that one destroys it (see __del__)
 
     def begin(self):
         if self.main is None:
@@ -280,12 +282,15 @@ class StepStreams:
         """executor state (csrc/runlist.hip) bound to this step's streams, created at its first use; call after begin()"""
         if self._runner is None:
             self._runner = C.c_void_p(_lib.load().ksmi_runner_create())
+            self._runner_pid = os.getpid()
             self._bind_runner()
         return self._runner
 
     def __del__(self):
+        # only in the process that created the runner: a forked DataLoader worker that collects an inherited copy of this object
+        # must not call hipEventDestroy (the HIP runtime does not survive a fork: the worker dies with a segmentation fault)
         try:
-            if self._runner is not None:
+            if self._runner is not None and self._runner_pid == os.getpid():
                 _lib.load().ksmi_runner_destroy(self._runner)
         except Exception:
             pass

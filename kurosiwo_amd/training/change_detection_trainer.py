@@ -107,7 +107,7 @@ def train_change_detection(model, train_loader, val_loader, test_loader, configs
         metrics.reset()
         loss_acc = torch.zeros(3, dtype=torch.float32, device=dev)
         nb = 0
-        for index, batch in enumerate(train_loader):
+        for index, batch in enumerate(D.before_fork(train_loader)):
             batch = D.shard_batch(batch)            # this rank's contiguous slice of the global batch (§8(e))
             if fused:
                 (xA, xB, xdem), mask = _fused_inputs(batch, configs)
@@ -171,7 +171,7 @@ def eval_change_detection(model, loader, settype, configs=None, model_configs=No
     total_loss = torch.zeros((), dtype=torch.float32, device=dev)
     nsamples = 0
     with torch.no_grad():
-        for batch in loader:
+        for batch in D.before_fork(loader):
             batch = D.shard_batch(batch, even=False)
             if len(batch) == 0:        # this rank's slice of a ragged last batch is empty (n % batch < world): nothing to evaluate,
                 continue               # the all-reduce below still runs once on every rank

@@ -39,7 +39,7 @@ def train_semantic_segmentation(model, train_loader, val_loader, test_loader, co
         metrics.reset()
         loss_acc = torch.zeros(3, dtype=torch.float32, device=dev)
         nb = 0
-        for index, batch in enumerate(train_loader):
+        for index, batch in enumerate(D.before_fork(train_loader)):
             batch = D.shard_batch(batch)
             image, mask = seg_inputs(batch, configs["inputs"], bool(configs["dem"]))
             if step is None or step.B != image.shape[0]:
@@ -84,7 +84,7 @@ def eval_semantic_segmentation(model, loader, configs=None, settype="Test", mode
     total_loss = torch.zeros((), dtype=torch.float32, device=dev)
     nsamples = 0
     with torch.no_grad():
-        for batch in loader:
+        for batch in D.before_fork(loader):
             batch = D.shard_batch(batch, even=False)
             if len(batch) == 0:        # empty slice of a ragged last batch on this rank (see eval_change_detection)
                 continue
