@@ -720,6 +720,15 @@ int ksmi_augment_views(const float* x, const int32_t* params, const int32_t* fal
                        void* stream);
 int ksmi_augment_masks(const void* x, void* y, const int32_t* params, const int32_t* fallback, int32_t* count, int B, int H, int W, int elem_bytes,
                        void* stream);
+/* The slope of the DEM channel on the device (csrc/terrain.hip): what --slope does in dataset/Dataset.py:747-761 (GRD) and :1160-1171
+ * (SLC) with richdem.TerrainAttribute(attrib="slope_riserun") and the standardisation behind it, for n contiguous fp32 tiles of
+ * H x W at once; out must not overlap dem.  Horn's 3 x 3 differences at cell size 1 in double, operation for operation what
+ * kurosiwo_amd/dataset.py:slope_riserun computes on the host, so the result carries the same bits: a neighbour outside its own tile,
+ * a NaN neighbour, or one whose widened value equals `nodata` takes the centre's value; a centre equal to `nodata` gives
+ * (float)nodata.  The sentinel is compared in double against the widened fp32 cell, as on the host: one that fp32 cannot represent
+ * (3.4e38) matches nothing.  nodata = NaN: no sentinel.  standardise != 0: (o - mean) / stdv in fp32 (torch's sub then div).
+ * n = 0 is a no-op; n < 0, H < 1, W < 1, a null pointer or overlapping buffers are KSMI_E_ARG and launch nothing. */
+int ksmi_dem_slope(const float* dem, float* out, int n, int H, int W, double nodata, float mean, float stdv, int standardise, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

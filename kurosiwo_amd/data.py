@@ -111,7 +111,7 @@ def _archive_loaders(configs, kind, bs, workers):
     plain = dict(configs, data_augmentations=False) if pipeline is not None else configs
     ds = {m: cls(mode=m, configs=plain) for m in ("train", "val", "test")}
     batch_level = ((kind == "slc" or configs.get("clamp_input") is not None) and configs.get("scale_input") == "normalize"
-                   and not configs.get("uint8") and not configs.get("slope") and not configs.get("oversampling")
+                   and not configs.get("uint8") and not configs.get("oversampling")
                    and configs.get("gpu_input_pipeline", True) and str(configs.get("device", "cuda")).startswith("cuda")
                    and torch.cuda.is_available())
     if pipeline is not None and not (batch_level and kind == "grd"):

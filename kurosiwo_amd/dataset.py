@@ -510,14 +510,24 @@ class TileBatchLoader:
     augment: a kurosiwo_amd.augment.Pipeline (GRD, train mode, CUDA only): the `data_augmentations` views of Dataset.create_views
     (dataset/Dataset.py:171-190, 792-805) rendered on the device.  The three dates of a sample share one parameter row; the label and
     the valid mask (MK0_MNA) take the nearest-neighbour view; a sample whose augmented valid mask is empty comes back un-augmented,
-    decided on the device (no host sync).  With raw=True the views are clamped but not normalised."""
+    decided on the device (no host sync).  With raw=True the views are clamped but not normalised.
+    slope (configs["slope"] with configs["dem"]; dataset/Dataset.py:747-761, 1160-1171): the terrain position of the tuple holds the
+    standardised slope_riserun of the gap-filled DEM, one ksmi_dem_slope launch per batch on the copy stream, bit for bit the value of
+    the per-sample classes.  Those hand slope_riserun each file's own no-data value; a batch uses the value of its FIRST DEM file
+    (one archive writes one sentinel; the SLC batch path already reads it there).  Views leave the terrain channel alone, slope or
+    DEM (create_views gets the dates and the masks only, :793-796)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, drop_last=False, device="cuda", threads=8, raw=False, rank=0, world=1, seed=None,
                  prefetch=2, augment=None):
         cfg = dataset.configs
         self.slc = isinstance(dataset, SLCDataset)
-        if not isinstance(dataset, (Dataset, SLCDataset)) or cfg["scale_input"] != "normalize" or cfg.get("uint8") or cfg.get("slope"):
-            raise ValueError("TileBatchLoader: Dataset / SLCDataset with scale_input 'normalize' (no uint8, no slope)")
+        if not isinstance(dataset, (Dataset, SLCDataset)) or cfg["scale_input"] != "normalize" or cfg.get("uint8"):
+            raise ValueError("TileBatchLoader: Dataset / SLCDataset with scale_input 'normalize' (no uint8)")
+        if cfg.get("slope") and not cfg["dem"]:                                   # dataset/Dataset.py:741-745
+            print("To return the slope the DEM option must be enabled. Validate the config file!")
+            raise SystemExit(2)
+        if cfg.get("slope") and torch.device(device).type != "cuda":
+            raise RuntimeError("TileBatchLoader computes the slope on the GPU (Dataset[i] / SLCDataset[i] are the CPU path)")
         if not self.slc and cfg["clamp_input"] is None:
             raise ValueError("TileBatchLoader: clamp_input is required (the GPU preprocess clamps)")
         if augment is not None and (self.slc or dataset.mode != "train" or torch.device(device).type != "cuda" or cfg.get("oversampling")):
@@ -643,6 +653,7 @@ class TileBatchLoader:
         """4-band tiles (dataset/Dataset.py:1087-1228): [n x (MS1, SL1, SL2) x 4 bands][DEM][masks] in the staging buffer, Normalize on the
         device.  A batch with a ragged tile (smaller than 224 x 224: padded by the reference, :1173-1207) takes the per-sample path."""
         from .data import preprocess_gpu
+        from .functional import dem_slope
         ds, cfg, dev, n = self.ds, self.ds.configs, self.device, len(indices)
         dem = bool(cfg["dem"])
         samples, files = zip(*[ds.sample_files(i) for i in indices]) if n else ((), ())
@@ -678,7 +689,9 @@ class TileBatchLoader:
         flood, sec1, sec2 = dates
         sv = lambda v: [torch.full((n,), float(x), dtype=torch.float64) for x in v]
         out = [sv(means), sv(stds), flood, mask, sv(means), sv(stds), sec1, sv(means), sv(stds), sec2]
-        if dem:
+        if dem and cfg.get("slope"):
+            out.append(dem_slope(dems, nodata, cfg["slc_slope_mean"], cfg["slc_slope_std"]))          # on the copy stream, like the expression below
+        elif dem:
             out.append((dems - torch.as_tensor(cfg["slc_dem_mean"], dtype=torch.float32, device=dev).view(1, -1, 1, 1)) /
                        torch.as_tensor(cfg["slc_dem_std"], dtype=torch.float32, device=dev).view(1, -1, 1, 1))
         out += [torch.tensor([s["clz"] for s in samples], dtype=torch.int64), torch.tensor([s["activation"] for s in samples], dtype=torch.int64)]
@@ -686,6 +699,7 @@ class TileBatchLoader:
 
     def _load_grd(self, indices):
         from .data import preprocess_gpu
+        from .functional import dem_slope
         ds, cfg, dev, n = self.ds, self.ds.configs, self.device, len(indices)
         dem = bool(cfg["dem"])
         samples, files = zip(*[ds.sample_files(i) for i in indices]) if n else ((), ())
@@ -703,7 +717,7 @@ class TileBatchLoader:
         sar = stage[:6 * n].view(n, 6, TILE, TILE).to(dev, non_blocking=True)
         k = 6 * n
         dems = None
-        if dem:                                                   # gaps filled on the host (in the staging buffer), standardised on the device
+        if dem:                                                   # gaps filled on the host (in the staging buffer), standardised (or turned into the slope) on the device
             dems = geotiff.fill_nodata(stage[k:k + n], threads=self.threads).view(n, 1, TILE, TILE).to(dev, non_blocking=True)
             k += n
         mask = stage[k:k + len(with_mask)].to(dev, non_blocking=True).long()
@@ -742,7 +756,10 @@ class TileBatchLoader:
         flood, pre1, pre2 = dates
         sv = lambda v: [torch.full((n,), float(x), dtype=torch.float64) for x in v]
         out = [sv(means), sv(stds), flood, mask, sv(means), sv(stds), pre1, sv(means), sv(stds), pre2]
-        if dem:
+        if dem and cfg.get("slope"):
+            nodata = geotiff.info(files[0]["MK0_DEM"])["nodata"] if n else None                          # the batch's first DEM file
+            out.append(dem_slope(dems, nodata, cfg["slope_mean"], cfg["slope_std"]))                  # on the copy stream, like the expression below
+        elif dem:
             out.append((dems - torch.as_tensor(cfg["dem_mean"], dtype=torch.float32, device=dev).view(1, -1, 1, 1)) /
                        torch.as_tensor(cfg["dem_std"], dtype=torch.float32, device=dev).view(1, -1, 1, 1))
         out += [torch.tensor([s["clz"] for s in samples], dtype=torch.int64), torch.tensor([s["activation"] for s in samples], dtype=torch.int64)]

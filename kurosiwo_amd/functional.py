@@ -357,6 +357,36 @@ def bilinear_backward(dy, Hi, Wi, out=None):
     return out
 
 
+def _one_scalar(v, name):
+    """a scalar or a one-element list (data_config.json: slope_mean is a scalar, dem_mean a list) -> float"""
+    if isinstance(v, (list, tuple)) or (torch.is_tensor(v) and v.dim() > 0):
+        if len(v) != 1:
+            raise ValueError(f"dem_slope: {name} is one value (the terrain channel), got {len(v)}")
+        v = v[0]
+    return float(v)
+
+
+def dem_slope(dem, nodata=None, mean=None, std=None, out=None):
+    """ksmi_dem_slope: the slope_riserun of every H x W tile of a contiguous fp32 CUDA tensor [..., H, W], bit for bit what
+    kurosiwo_amd.dataset.slope_riserun(tile, nodata) gives on the host; with mean / std (a scalar or a one-element list, both or
+    neither) followed by (slope - mean) / std in fp32.  nodata None or NaN: no sentinel.  Runs on the current stream."""
+    require_gpu(dem)
+    if dem.dtype != torch.float32 or dem.dim() < 2 or not dem.is_contiguous():
+        raise ValueError("dem_slope: a contiguous float32 tensor [..., H, W]")
+    if (mean is None) != (std is None):
+        raise ValueError("dem_slope: mean and std come together (None for both: no standardisation)")
+    if out is None:
+        out = torch.empty_like(dem)
+    elif out.dtype != torch.float32 or out.shape != dem.shape or out.device != dem.device or not out.is_contiguous():
+        raise ValueError("dem_slope: out is a contiguous float32 tensor of dem's shape on dem's device")
+    H, W = dem.shape[-2:]
+    n = dem.numel() // (H * W) if H * W else 0
+    m, s = (0.0, 1.0) if mean is None else (_one_scalar(mean, "mean"), _one_scalar(std, "std"))
+    _lib.check(_lib.load().ksmi_dem_slope(dem.data_ptr(), out.data_ptr(), n, H, W, float("nan") if nodata is None else float(nodata), m, s,
+                                          0 if mean is None else 1, stream_ptr()), "dem_slope")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # token GEMMs on the 128x128 MFMA tiles (gemm.hip, bf16)
 # ---------------------------------------------------------------------------------------------------

@@ -65,7 +65,7 @@ def fuse_input_pipeline(model, loaders, configs):
     if not (hasattr(model, "set_input_pipeline") and all(isinstance(ld, TileBatchLoader) and not ld.slc for ld in loaders)
             and configs.get("fuse_input_pipeline", True) and os.environ.get("KSMI_FUSE_INPUT", "1") != "0"):
         return False
-    ndem = 1 if configs["dem"] else 0        # the DEM arrives standardised (its gap filling is host work): identity for that channel
+    ndem = 1 if configs["dem"] else 0        # the DEM or slope arrives standardised (the gap filling is host work): identity for that channel
     model.set_input_pipeline(list(configs["data_mean"]) + [0.0] * ndem, list(configs["data_std"]) + [1.0] * ndem,
                              [configs["clamp_input"]] * len(configs["data_mean"]) + [-1.0] * ndem)
     for ld in loaders:
