@@ -729,6 +729,33 @@ int ksmi_augment_masks(const void* x, void* y, const int32_t* params, const int3
  * (3.4e38) matches nothing.  nodata = NaN: no sentinel.  standardise != 0: (o - mean) / stdv in fp32 (torch's sub then div).
  * n = 0 is a no-op; n < 0, H < 1, W < 1, a null pointer or overlapping buffers are KSMI_E_ARG and launch nothing. */
 int ksmi_dem_slope(const float* dem, float* out, int n, int H, int W, double nodata, float mean, float stdv, int standardise, void* stream);
+/* Whole-scene inference on the device (csrc/scene.hip; kurosiwo_amd/scene.py, predict.py).  The windows of a scene [Hs][Ws] form a
+ * product grid: row origins ys[ny], column origins xs[nx] (sorted int32 device arrays, never negative), window i = iy * nx + ix is
+ * h x w at (ys[iy], xs[ix]); it overhangs the scene only at the bottom / right, when the scene is smaller than the window.  Every
+ * entry takes the windows i0 .. i0 + n - 1: n = 0 is a no-op; n < 0, i0 < 0, i0 + n > ny * nx, a size < 1 or a null pointer are
+ * KSMI_E_ARG and launch nothing.
+ *   ksmi_scene_valid: replaces a host pass of np.isnan / == nodata over every input raster.  valid[p] = (first ? 1 : valid[p]) &
+ *   (no channel of raster [C][HW] at p is NaN or equal to nodata); nodata = NaN: no sentinel. */
+int ksmi_scene_valid(const float* raster, int C, int64_t HW, float nodata, unsigned char* valid, int first, void* stream);
+/* ksmi_scene_gather: replaces host cropping plus one ksmi_sar_preprocess call per crop.  out [n][C][h][w] fp32 from raster
+ * [C][Hs][Ws] fp32: a value equal to nodata counts as NaN, then exactly ksmi_sar_preprocess per channel (clamp[c] >= 0: clamp to
+ * [0, clamp], NaN -> clamp; clamp[c] < 0: no clamp, NaN -> mean; then (v - mean) / std); mean NULL: the raw value with nodata ->
+ * NaN; cells of a window outside the scene are 0.0f. */
+int ksmi_scene_gather(const float* raster, int C, int Hs, int Ws, const int32_t* ys, int ny, const int32_t* xs, int nx, int i0, int n, int h,
+                      int w, const float* mean, const float* stdv, const float* clamp, float nodata, float* out, void* stream);
+/* ksmi_scene_accumulate: replaces the Python loop of acc[:, y:y+h, x:x+w] += weight * logits slices (or a scatter-add with float
+ * atomics).  logits [n][K][h][w] fp32 of windows i0 ..; weight [h][w]; acc [K][Hs][Ws] and wsum [Hs][Ws] fp32, zeroed by the caller
+ * before the first launch.  Per scene pixel, over the covering windows of this launch in ascending i: acc_k = acc_k + (weight *
+ * logit_k), wsum = wsum + weight, product and sum rounded separately; no atomics: bitwise reproducible, across launches the result
+ * depends on stream order only.  1 <= K <= 8. */
+int ksmi_scene_accumulate(const float* logits, const int32_t* ys, int ny, const int32_t* xs, int nx, int i0, int n, int K, int h, int w,
+                          const float* weight, float* acc, float* wsum, int Hs, int Ws, void* stream);
+/* ksmi_scene_finalize: replaces acc / wsum, argmax(0) and softmax(0) over the scene.  m_k = acc_k / wsum; out_class_u8[p] = the
+ * first maximum of m (lowest index on ties), or invalid_class where valid[p] == 0 (valid NULL: every pixel counts); out_score (NULL,
+ * or [K][HW] fp32): m (score_mode 0) or softmax(m) with the maximum subtracted first (score_mode 1), NaN at invalid pixels.  wsum
+ * must be positive everywhere (a grid that covers the scene); 1 <= K <= 8. */
+int ksmi_scene_finalize(const float* acc, const float* wsum, const unsigned char* valid, int K, int64_t HW, int invalid_class,
+                        unsigned char* out_class_u8, float* out_score, int score_mode, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -2,8 +2,9 @@
 
 Reading is native (kurosiwo_amd/csrc/tile_reader.hip behind ksmi_tiff_* / ksmi_tile_batch_read): it replaces the reference's
 cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728) and rioxarray.open_rasterio for the DEM (:730-737).
-`write` is a small pure-numpy TIFF writer: it exists to build synthetic archives and test fixtures (tools/make_synthetic_archive.py),
-the product path never writes tiles."""
+`write` is a small pure-numpy TIFF writer: it builds synthetic archives and test fixtures (tools/make_synthetic_archive.py), and it
+writes the products of whole-scene inference (predict.py: the uint8 class raster and the float32 scores, Deflate in tiles of 256 with
+the georeferencing of the input); training and evaluation never write tiles."""
 import ctypes as C
 import struct
 import zlib
@@ -89,7 +90,7 @@ def fill_nodata(tiles, threads=1):
     return tiles
 
 
-# ------------------------------------------------------------------------------------------------ writer (fixtures, synthetic archives)
+# ------------------------------------------------------------------------------------------------ writer (fixtures, synthetic archives, scene maps)
 def _lzw_encode(data):
     """TIFF 6.0 §13 LZW: MSB-first, 9..12 bits, early change"""
     out = bytearray()

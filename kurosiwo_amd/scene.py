@@ -1,0 +1,233 @@
+"""Whole-scene inference: a trained model over a raster larger than its 224 x 224 tiles (csrc/scene.hip).
+
+The scene's rasters live on the device.  `predict_scene` walks a product grid of overlapping windows in batches: one
+ksmi_scene_gather per input raster cuts and normalises the batch's windows (the arithmetic of ksmi_sar_preprocess), the model runs
+under torch.no_grad(), and one ksmi_scene_accumulate adds weight * logits onto the scene in gather form (one thread per scene pixel,
+the covering windows in ascending order, no atomics: the blend is bitwise reproducible and equals the numpy slice loop of
+tests/scene_ref.py).  ksmi_scene_valid marks the pixels where some input is NaN or the nodata sentinel, ksmi_scene_finalize divides
+by the summed weights and takes the first maximum.  Everything runs on the current stream; nothing synchronises."""
+import numpy as np
+import torch
+
+from . import _lib
+from .runtime import require_gpu, stream_ptr
+
+MAX_CLASSES = 8                   # SCENE_MAX_K of csrc/scene.hip
+SCORES = {None: None, "logits": 0, "softmax": 1}
+
+
+def _axis(L, win, s):
+    if not 1 <= s <= win:
+        raise ValueError(f"window_grid: 1 <= stride <= window, got stride {s} for window {win}")
+    if L < 1:
+        raise ValueError(f"window_grid: a scene of {L} pixels")
+    if L < win:
+        return [0]
+    o = list(range(0, L - win + 1, s))
+    if o[-1] + win != L:
+        o.append(L - win)                # the last window ends flush with the border
+    return o
+
+
+def window_grid(Hs, Ws, h, w, sy, sx):
+    """(ys, xs): int32 row and column origins of the product grid of h x w windows at strides (sy, sx) over an Hs x Ws scene; per
+    axis range(0, L - win + 1, stride) plus L - win when the last window would not end at the border, [0] when L < win."""
+    return np.asarray(_axis(Hs, h, sy), np.int32), np.asarray(_axis(Ws, w, sx), np.int32)
+
+
+def blend_weights(h, w, kind="hann"):
+    """[h, w] float32: "uniform" = ones; "hann" = float32(a[y] * a[x]), a[i] = 0.5 - 0.5 cos(2 pi (i + 0.5) / L) in float64 (the
+    half-sample shift keeps every weight strictly positive), the product taken in float64 and rounded once."""
+    if h < 1 or w < 1:
+        raise ValueError("blend_weights: h, w >= 1")
+    if kind == "uniform":
+        return np.ones((h, w), np.float32)
+    if kind != "hann":
+        raise ValueError(f'blend_weights: kind is "uniform" or "hann", got {kind!r}')
+    a = lambda L: 0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(L, dtype=np.float64) + 0.5) / L)
+    return (a(h)[:, None] * a(w)[None, :]).astype(np.float32)
+
+
+def _nodata(v):
+    return float("nan") if v is None else float(v)
+
+
+def _check_raster(r, name):
+    require_gpu(r)
+    if r.dtype != torch.float32 or r.dim() != 3 or not r.is_contiguous() or r.shape[0] < 1:
+        raise ValueError(f"{name}: a contiguous float32 tensor [C, Hs, Ws]")
+
+
+# ---------------------------------------------------------------------------------------------------- thin wrappers of the C-ABI
+def scene_valid(raster, nodata=None, valid=None):
+    """ksmi_scene_valid: valid uint8 [Hs, Ws] = (valid given: valid &) no channel of raster [C, Hs, Ws] is NaN or equal to nodata"""
+    _check_raster(raster, "scene_valid")
+    C, Hs, Ws = raster.shape
+    first = valid is None
+    if first:
+        valid = torch.empty((Hs, Ws), dtype=torch.uint8, device=raster.device)
+    elif valid.dtype != torch.uint8 or valid.shape != (Hs, Ws) or valid.device != raster.device or not valid.is_contiguous():
+        raise ValueError("scene_valid: valid is a contiguous uint8 tensor [Hs, Ws] on the raster's device")
+    _lib.check(_lib.load().ksmi_scene_valid(raster.data_ptr(), C, Hs * Ws, _nodata(nodata), valid.data_ptr(), 1 if first else 0, stream_ptr()),
+               "scene_valid")
+    return valid
+
+
+def _check_grid(ys, xs, name):
+    for o in (ys, xs):
+        require_gpu(o)
+        if o.dtype != torch.int32 or o.dim() != 1 or not o.is_contiguous() or o.numel() < 1:
+            raise ValueError(f"{name}: ys and xs are contiguous int32 device vectors")
+
+
+def scene_gather(raster, ys, xs, i0, n, h, w, norm=None, nodata=None, out=None):
+    """ksmi_scene_gather: windows i0 .. i0 + n - 1 of raster [C, Hs, Ws] as [n, C, h, w]; norm = (mean, std, clamp) float32 device
+    vectors of C entries, or None for raw values (nodata -> NaN)"""
+    _check_raster(raster, "scene_gather")
+    _check_grid(ys, xs, "scene_gather")
+    C, Hs, Ws = raster.shape
+    if out is None:
+        out = torch.empty((max(n, 0), C, h, w), dtype=torch.float32, device=raster.device)
+    elif out.dtype != torch.float32 or out.shape != (n, C, h, w) or out.device != raster.device or not out.is_contiguous():
+        raise ValueError("scene_gather: out is a contiguous float32 tensor [n, C, h, w] on the raster's device")
+    if norm is not None:
+        for t in norm:
+            if t.dtype != torch.float32 or t.numel() != C or t.device != raster.device or not t.is_contiguous():
+                raise ValueError(f"scene_gather: mean, std and clamp are float32 device vectors of {C} entries")
+    m, s, c = (None, None, None) if norm is None else (t.data_ptr() for t in norm)
+    _lib.check(_lib.load().ksmi_scene_gather(raster.data_ptr(), C, Hs, Ws, ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, h, w,
+                                             m, s, c, _nodata(nodata), out.data_ptr(), stream_ptr()), "scene_gather")
+    return out
+
+
+def scene_accumulate(logits, ys, xs, i0, weight, acc, wsum):
+    """ksmi_scene_accumulate: acc [K, Hs, Ws] += weight [h, w] * logits [n, K, h, w] of windows i0 ..; wsum [Hs, Ws] += weight"""
+    require_gpu(logits)
+    _check_grid(ys, xs, "scene_accumulate")
+    if logits.dtype != torch.float32 or logits.dim() != 4 or not logits.is_contiguous():
+        raise ValueError("scene_accumulate: logits is a contiguous float32 tensor [n, K, h, w]")
+    n, K, h, w = logits.shape
+    if acc.dim() != 3 or acc.shape[0] != K or wsum.shape != acc.shape[1:] or weight.shape != (h, w) or any(
+            t.dtype != torch.float32 or not t.is_contiguous() or t.device != logits.device for t in (weight, acc, wsum)):
+        raise ValueError("scene_accumulate: float32 contiguous weight [h, w], acc [K, Hs, Ws] and wsum [Hs, Ws] on the logits' device")
+    _lib.check(_lib.load().ksmi_scene_accumulate(logits.data_ptr(), ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, K, h, w,
+                                                 weight.data_ptr(), acc.data_ptr(), wsum.data_ptr(), acc.shape[1], acc.shape[2], stream_ptr()),
+               "scene_accumulate")
+
+
+def scene_finalize(acc, wsum, valid=None, score=None, invalid_class=3):
+    """ksmi_scene_finalize -> (classes uint8 [Hs, Ws], scores float32 [K, Hs, Ws] or None); score: None, "logits" (the blended mean
+    logits) or "softmax"; invalid pixels get `invalid_class` and NaN scores"""
+    require_gpu(acc)
+    if score not in SCORES:
+        raise ValueError(f'scene_finalize: score is None, "logits" or "softmax", got {score!r}')
+    if acc.dtype != torch.float32 or acc.dim() != 3 or not acc.is_contiguous() or wsum.dtype != torch.float32 or wsum.shape != acc.shape[1:] \
+            or not wsum.is_contiguous() or wsum.device != acc.device:
+        raise ValueError("scene_finalize: float32 contiguous acc [K, Hs, Ws] and wsum [Hs, Ws]")
+    K, Hs, Ws = acc.shape
+    if valid is not None and (valid.dtype != torch.uint8 or valid.shape != (Hs, Ws) or not valid.is_contiguous() or valid.device != acc.device):
+        raise ValueError("scene_finalize: valid is a contiguous uint8 tensor [Hs, Ws]")
+    cls = torch.empty((Hs, Ws), dtype=torch.uint8, device=acc.device)
+    out = None if score is None else torch.empty_like(acc)
+    _lib.check(_lib.load().ksmi_scene_finalize(acc.data_ptr(), wsum.data_ptr(), None if valid is None else valid.data_ptr(), K, Hs * Ws,
+                                               int(invalid_class), cls.data_ptr(), None if out is None else out.data_ptr(), SCORES[score] or 0,
+                                               stream_ptr()), "scene_finalize")
+    return cls, out
+
+
+# ---------------------------------------------------------------------------------------------------- the scene loop
+def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, weight="hann", nodata=None, score=None, raw=False,
+                  invalid_class=3):
+    """A class map of a whole scene.
+
+    rasters: device float32 [C_i, Hs, Ws], one per model input (e.g. pre, post, DEM), all of one size.
+    norms:   per raster (mean, std, clamp), each one value per channel: clamp >= 0 clamps to [0, clamp] and maps NaN to clamp,
+             clamp < 0 leaves the value and maps NaN to the mean (the DEM); then (v - mean) / std.
+    forward: callable on the list of [B, C_i, h, w] window batches -> logits [B, K, h, w] (cd_forward / seg_forward, or any stub).
+    window, stride: of the square windows, 1 <= stride <= window; weight: "hann" or "uniform" (blend_weights).
+    nodata:  the sentinel of the rasters (None: only NaN is missing); one value, or one per raster.
+    raw:     gather raw values (nodata -> NaN) for a model that normalises inside its first convolution (cd_forward(..., norms)).
+    score:   None, "logits" (the blended mean logits) or "softmax".
+    Returns (classes uint8 [Hs, Ws] with `invalid_class` where some input is missing, scores float32 [K, Hs, Ws] or None)."""
+    if score not in SCORES:
+        raise ValueError(f'predict_scene: score is None, "logits" or "softmax", got {score!r}')
+    if not rasters or len(norms) != len(rasters):
+        raise ValueError("predict_scene: one (mean, std, clamp) per raster")
+    for r in rasters:
+        _check_raster(r, "predict_scene: every raster")
+    dev = rasters[0].device
+    Hs, Ws = rasters[0].shape[1:]
+    if any(r.shape[1:] != (Hs, Ws) or r.device != dev for r in rasters):
+        raise ValueError("predict_scene: the rasters have one size and one device")
+    nodatas = list(nodata) if isinstance(nodata, (list, tuple)) else [nodata] * len(rasters)
+    if len(nodatas) != len(rasters):
+        raise ValueError("predict_scene: nodata is one value or one per raster")
+    h = w = int(window)
+    sy = sx = int(stride)
+    if int(batch) < 1:
+        raise ValueError("predict_scene: batch >= 1")
+    ys_h, xs_h = window_grid(Hs, Ws, h, w, sy, sx)
+    wt_h = blend_weights(h, w, weight)            # strictly positive on a grid that covers the scene: wsum > 0 at every pixel
+    dev_norms = []
+    for r, nm in zip(rasters, norms):
+        vecs = [torch.as_tensor([float(v) for v in (p if hasattr(p, "__len__") else [p] * r.shape[0])], dtype=torch.float32) for p in nm]
+        if len(vecs) != 3 or any(v.numel() != r.shape[0] for v in vecs) or bool((vecs[1] == 0).any()):
+            raise ValueError("predict_scene: a norm is (mean, std, clamp) with one non-zero std per channel of its raster")
+        dev_norms.append(None if raw else tuple(v.to(dev) for v in vecs))
+    ys, xs, wt = torch.from_numpy(ys_h).to(dev), torch.from_numpy(xs_h).to(dev), torch.from_numpy(wt_h).to(dev)
+    total = len(ys_h) * len(xs_h)
+    acc = wsum = None
+    with torch.no_grad():
+        for i0 in range(0, total, int(batch)):
+            n = min(int(batch), total - i0)                               # the ragged last batch passes its own n
+            tiles = [scene_gather(r, ys, xs, i0, n, h, w, nm, nd) for r, nm, nd in zip(rasters, dev_norms, nodatas)]
+            logits = forward(tiles).float().contiguous()
+            if logits.dim() != 4 or logits.shape[0] != n or logits.shape[2:] != (h, w) or not 1 <= logits.shape[1] <= MAX_CLASSES:
+                raise ValueError(f"predict_scene: forward returned {tuple(logits.shape)}, expected [{n}, K <= {MAX_CLASSES}, {h}, {w}]")
+            if acc is None:
+                acc = torch.zeros((logits.shape[1], Hs, Ws), dtype=torch.float32, device=dev)
+                wsum = torch.zeros((Hs, Ws), dtype=torch.float32, device=dev)
+            scene_accumulate(logits, ys, xs, i0, wt, acc, wsum)
+        valid = None
+        for r, nd in zip(rasters, nodatas):
+            valid = scene_valid(r, nd, valid)
+        return scene_finalize(acc, wsum, valid, score, invalid_class)
+
+
+# ---------------------------------------------------------------------------------------------------- model adapters
+def cd_forward(model, method, norms=None):
+    """forward for predict_scene over rasters [date A, date B(, dem)]: model(xA, xB[, dem]); the last output for ChangeFormer, as
+    eval_change_detection takes it.  norms (the list predict_scene gets; use with raw=True): the model normalises inside its first
+    convolution, configured as training.change_detection_trainer.fuse_input_pipeline does (the date's channels, then the DEM's)."""
+    if norms is not None:
+        if not hasattr(model, "set_input_pipeline"):
+            raise _lib.KsmiError(f"{type(model).__name__} has no fused input pipeline: predict with raw=False")
+        as_lists = lambda nm: [[float(v) for v in p] for p in nm]
+        if len(norms) < 2 or as_lists(norms[0]) != as_lists(norms[1]):
+            raise ValueError("cd_forward: the two dates share one (mean, std, clamp)")
+        per = [[float(v) for nm in (list(norms[:1]) + list(norms[2:])) for v in nm[j]] for j in range(3)]
+        model.set_input_pipeline(*per)
+    own_tail = hasattr(model, "set_input_pipeline")            # SNUNet_ECAM.forward(xA, xB, dem): the concat as an address choice
+
+    def forward(xs):
+        xa, xb = xs[0], xs[1]
+        if len(xs) == 3 and own_tail:
+            out = model(xa, xb, xs[2])
+        elif len(xs) == 3:
+            out = model(torch.cat((xa, xs[2]), dim=1), torch.cat((xb, xs[2]), dim=1))
+        else:
+            out = model(xa, xb)
+        return out[-1] if str(method).lower() == "changeformer" else out
+    return forward
+
+
+def seg_forward(model, inputs=("pre_event_1", "pre_event_2", "post_event"), dem=False):
+    """forward for predict_scene over rasters [post, (dem), then the pre-event dates in the order of synthetic.seg_inputs]: their
+    channel concatenation, which is all seg_inputs does once the rasters are in that order"""
+    want = 1 + (1 if dem else 0) + len(set(inputs) - {"post_event"})
+
+    def forward(xs):
+        if len(xs) != want:
+            raise ValueError(f"seg_forward: {want} rasters for inputs {tuple(inputs)}" + (" with the DEM" if dem else "") + f", got {len(xs)}")
+        return model(xs[0] if len(xs) == 1 else torch.cat(xs, dim=1))
+    return forward

@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Map a whole Sentinel-1 scene with a trained checkpoint: windowed inference with on-device blending (kurosiwo_amd/scene.py).
+
+  python predict.py --task cd --method snunet --checkpoint best.pt \\
+      --post VV.tif VH.tif --pre1 VV.tif VH.tif [--pre2 ...] [--dem dem.tif] \\
+      --out flood.tif [--score softmax --score_out prob.tif] \\
+      [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16]
+
+Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
+nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
+("Invalid pixels").  The DEM's gaps are filled on the host as the loaders fill them, and the DEM is standardised with the loaders'
+constants.  The class raster is a Deflate-compressed uint8 GeoTIFF in tiles of 256 with the first post file's georeferencing and
+nodata = 3; the scores, where asked for, a float32 multi-band file written the same way.  The scene, the accumulators and the outputs
+live on one device: a scene that does not fit is outside this tool, as are --slope, SLC products and test-time flips."""
+import argparse
+import os
+import sys
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from kurosiwo_amd import geotiff                                            # noqa: E402
+from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
+from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
+from kurosiwo_amd.scene import cd_forward, predict_scene, seg_forward       # noqa: E402
+
+CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
+
+parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+parser.add_argument("--task", choices=("cd", "segmentation"), default=None, help="default: what the method decides")
+parser.add_argument("--method", required=True)
+parser.add_argument("--backbone", default=None)
+parser.add_argument("--checkpoint", required=True)
+parser.add_argument("--post", nargs="+", required=True)
+parser.add_argument("--pre1", nargs="+", default=None)
+parser.add_argument("--pre2", nargs="+", default=None)
+parser.add_argument("--dem", default=None)
+parser.add_argument("--slope", action="store_true", default=False)
+parser.add_argument("--nodata", type=float, default=None, help="sentinel of the SAR rasters (default: each file's nodata tag)")
+parser.add_argument("--out", required=True)
+parser.add_argument("--score", choices=("logits", "softmax"), default=None)
+parser.add_argument("--score_out", default=None)
+parser.add_argument("--window", type=int, default=224)
+parser.add_argument("--stride", type=int, default=112)
+parser.add_argument("--weight", choices=("hann", "uniform"), default="hann")
+parser.add_argument("--batch_size", type=int, default=32)
+parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
+parser.add_argument("--raw", action="store_true", default=False,
+                    help="hand raw windows to a model that normalises inside its first convolution (snunet)")
+
+
+def read_date(paths, nodata):
+    """the files of one date -> (float32 [bands, H, W], sentinel or None, info of the first file)"""
+    parts, first, sentinel = [], None, nodata
+    for p in paths:
+        a, meta = geotiff.read(p, dtype=np.float32, squeeze=False)
+        if first is None:
+            first = meta
+        if nodata is None and meta["nodata"] is not None and not np.isnan(meta["nodata"]):
+            if sentinel is not None and sentinel != meta["nodata"]:
+                raise SystemExit(f"predict.py: the files of one date carry different nodata tags ({sentinel} and {meta['nodata']}): pass --nodata")
+            sentinel = meta["nodata"]
+        parts.append(a)
+    if any(a.shape[1:] != parts[0].shape[1:] for a in parts):
+        raise SystemExit(f"predict.py: rasters of different sizes: {[a.shape for a in parts]}")
+    return np.concatenate(parts, axis=0), sentinel, first
+
+
+def read_dem(path):
+    """the DEM as the loaders read it: the sentinel and NaN are gaps, filled from the nearest valid cell on the host"""
+    a, meta = geotiff.read(path, dtype=np.float32, squeeze=False)
+    if a.shape[0] != 1:
+        raise SystemExit(f"predict.py: the DEM has one band, {path} has {a.shape[0]}")
+    if meta["nodata"] is not None and not np.isnan(meta["nodata"]):
+        a[a == np.float32(meta["nodata"])] = np.nan
+    return geotiff.fill_nodata(np.ascontiguousarray(a))
+
+
+def load_model(configs, model_configs, checkpoint):
+    if configs["task"] == "cd":
+        configs["resume_checkpoint"] = checkpoint
+        return initialize_cd_model(configs, model_configs, "test")
+    model = initialize_segmentation_model(configs, model_configs)
+    ck = torch.load(checkpoint, map_location=configs["device"], weights_only=False)
+    if isinstance(ck, torch.nn.Module):                 # main.py saves the whole module for the segmentation task
+        return ck.to(configs["device"])
+    model.load_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck)
+    return model
+
+
+def main(argv=None):
+    args = parser.parse_args(argv)
+    if args.slope:
+        raise SystemExit("predict.py: --slope is not supported: the slope of a whole scene is not computed here (train and map with --dem)")
+    if (args.score is None) != (args.score_out is None):
+        raise SystemExit("predict.py: --score and --score_out come together")
+    method = args.method.lower()
+    task = args.task or ("cd" if method in CD_METHODS else "segmentation")
+    dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
+    if task == "cd" and len(dates) != 1:
+        raise SystemExit("predict.py: change detection takes --post and exactly one of --pre1 / --pre2")
+    inputs = [n for n, _ in dates] + ["post_event"]
+
+    configs = load_json5(os.path.join(ROOT, "configs", "config.json"))
+    configs["method"], configs["task"] = method, task
+    model_configs = load_json5(os.path.join(ROOT, "configs", "method", method, method.replace("-", "_") + ".json"))
+    if args.backbone is not None:
+        model_configs["backbone"] = args.backbone
+    configs.update(model_configs)
+    configs = update_config(configs, SimpleNamespace(inputs=inputs, dem=args.dem is not None, slope=False), root=ROOT)
+    configs["precision"] = args.precision
+    if configs.get("slc"):
+        raise SystemExit("predict.py: SLC products are not supported")
+    dev = torch.device(configs["device"])
+
+    post, post_nd, geo = read_date(args.post, args.nodata)
+    pres = [read_date(p, args.nodata) for _, p in dates]
+    sar = (list(configs["data_mean"]), list(configs["data_std"]), [configs["clamp_input"]] * len(configs["data_mean"]))
+    if task == "cd":                                    # the order of cd_inputs: [date A, date B(, dem)]
+        rasters, nodatas = [pres[0][0], post], [pres[0][1], post_nd]
+    else:                                               # the order of seg_inputs: [post(, dem), pre dates]
+        rasters, nodatas = [post], [post_nd]
+    norms = [sar] * len(rasters)
+    if args.dem is not None:
+        rasters.append(read_dem(args.dem))
+        nodatas.append(None)
+        norms = norms + [([configs["dem_mean"]], [configs["dem_std"]], [-1.0])]
+    if task != "cd":
+        rasters += [p[0] for p in pres]
+        nodatas += [p[1] for p in pres]
+        norms = norms + [sar] * len(pres)
+    if any(r.shape[1:] != post.shape[1:] for r in rasters):
+        raise SystemExit(f"predict.py: rasters of different sizes: {[tuple(r.shape) for r in rasters]}")
+    if any(r.shape[0] != len(n[0]) for r, n in zip(rasters, norms)):
+        raise SystemExit(f'predict.py: every date has the {len(sar[0])} bands {configs["channels"]}, got {[r.shape[0] for r in rasters]}')
+
+    model = load_model(configs, model_configs, args.checkpoint).eval()
+    if task == "cd":
+        forward = cd_forward(model, method, norms if args.raw else None)
+    else:
+        if args.raw:
+            raise SystemExit("predict.py: --raw needs a model with a fused input pipeline (snunet)")
+        forward = seg_forward(model, inputs, dem=args.dem is not None)
+    classes, score = predict_scene(forward, [torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in rasters], norms, window=args.window,
+                                   stride=args.stride, batch=args.batch_size, weight=args.weight, nodata=nodatas, score=args.score,
+                                   raw=args.raw)
+    where = dict(compression="deflate", tile=(256, 256), pixel_scale=geo["pixel_scale"], origin=geo["origin"])
+    geotiff.write(args.out, classes.cpu().numpy(), nodata=3, **where)
+    print(f"wrote {args.out}: {classes.shape[0]} x {classes.shape[1]} classes")
+    if score is not None:
+        geotiff.write(args.score_out, score.cpu().numpy(), nodata=float("nan"), **where)
+        print(f"wrote {args.score_out}: {score.shape[0]} bands of {args.score}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,165 @@
+"""Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
+
+    python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
+
+A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
+After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
+  pass       predict_scene end to end between two HIP events on the one stream -> windows/s and scene pixels/s
+  split      the same loop with an event after each stage of each batch: gather (one launch per raster), forward, accumulate, and
+             valid + finalize once per pass; the event pairs are read after the pass's final synchronise
+  blend A/B  the blend alone on one fixed batch of logits reused for every batch of the grid: ksmi_scene_accumulate against the same
+             sums written as the torch slice loop on the device (acc[:, y:y+h, x:x+w] += weight * logits[i]; wsum[...] += weight)
+  bytes/s    of the accumulate launches: logits read once, weight read per window cell, acc and wsum read and written once per touched
+             pixel per launch (counted from the grid), over their summed event time; next to the measured HBM rate the README quotes
+One json object per line on stdout, appended to --out when given."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+MEASURED_HBM_TBS = 5.9               # README.md: the box's measured HBM ceiling
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=4480)
+    ap.add_argument("--window", type=int, default=224)
+    ap.add_argument("--stride", type=int, default=112)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+    from kurosiwo_amd.config import load_json5
+    from kurosiwo_amd.scene import (blend_weights, cd_forward, predict_scene, scene_accumulate, scene_finalize, scene_gather, scene_valid,
+                                    window_grid)
+    from kurosiwo_amd.snunet import SNUNet_ECAM
+    if not torch.cuda.is_available():
+        raise SystemExit("scene_probe: no GPU: nothing here can be measured on the host")
+    data = load_json5(os.path.join(HERE, "configs", "train", "data_config.json"))
+    norm = (data["data_mean"], data["data_std"], [data["clamp_input"]] * 2)
+    dev, S, h, K = torch.device("cuda"), a.size, a.window, 3
+    g = torch.Generator(device="cpu").manual_seed(4480)
+    rasters = []
+    for _ in range(2):
+        r = (torch.randn((2, S, S), generator=g) * 0.08 + 0.06).to(dev)
+        r[0, 100:140, 200:260] = float("nan")
+        rasters.append(r)
+    torch.manual_seed(0)
+    model = SNUNet_ECAM(2, K, base_channel=32, precision=a.precision).to(dev).eval()
+    forward = cd_forward(model, "snunet")
+    ys_h, xs_h = window_grid(S, S, h, h, a.stride, a.stride)
+    total = len(ys_h) * len(xs_h)
+    starts = list(range(0, total, a.batch))
+    ys, xs = torch.from_numpy(ys_h).to(dev), torch.from_numpy(xs_h).to(dev)
+    wt = torch.from_numpy(blend_weights(h, h, "hann")).to(dev)
+    dev_norm = tuple(torch.tensor(v, dtype=torch.float32, device=dev) for v in norm)
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    med = statistics.median
+    lines = []
+
+    def emit(**kv):
+        line = json.dumps(kv)
+        print(line, flush=True)
+        lines.append(line)
+
+    def whole():
+        e0, e1 = ev(), ev()
+        e0.record()
+        out = predict_scene(forward, rasters, [norm, norm], window=h, stride=a.stride, batch=a.batch, weight="hann")
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out[0]
+
+    _, first = whole()                                                         # warm-up
+    runs = [whole() for _ in range(a.repeats)]
+    assert all(torch.equal(first, c) for _, c in runs)                         # the map is the same in every pass, bit for bit
+    t = med([ms for ms, _ in runs])
+    emit(what="pass", size=S, window=h, stride=a.stride, batch=a.batch, precision=a.precision, windows=total, batches=len(starts),
+         ms_median=round(t, 2), ms_all=[round(ms, 2) for ms, _ in runs], windows_per_s=round(total / t * 1e3, 1),
+         scene_mpixels_per_s=round(S * S / t * 1e-3, 2), classes=torch.bincount(first.flatten().long(), minlength=4).tolist())
+
+    def split():
+        marks, acc, wsum = [], torch.zeros((K, S, S), device=dev), torch.zeros((S, S), device=dev)
+        with torch.no_grad():
+            for i0 in starts:
+                n = min(a.batch, total - i0)
+                e = [ev() for _ in range(4)]
+                e[0].record()
+                tiles = [scene_gather(r, ys, xs, i0, n, h, h, dev_norm, None) for r in rasters]
+                e[1].record()
+                logits = forward(tiles).float().contiguous()
+                e[2].record()
+                scene_accumulate(logits, ys, xs, i0, wt, acc, wsum)
+                e[3].record()
+                marks.append(e)
+            f0, f1 = ev(), ev()
+            f0.record()
+            valid = None
+            for r in rasters:
+                valid = scene_valid(r, None, valid)
+            cls, _ = scene_finalize(acc, wsum, valid, None, 3)
+            f1.record()
+        torch.cuda.synchronize()
+        assert torch.equal(cls, first)
+        return [sum(e[j].elapsed_time(e[j + 1]) for e in marks) for j in range(3)] + [f0.elapsed_time(f1)]
+    parts = [split() for _ in range(a.repeats)]
+    gat, fwd, accu, fin = (med(p[j] for p in parts) for j in range(4))
+    emit(what="split", gather_ms=round(gat, 3), forward_ms=round(fwd, 2), accumulate_ms=round(accu, 3), valid_finalize_ms=round(fin, 3),
+         scene_kernels_ms=round(gat + accu + fin, 3), scene_kernels_over_forward=round((gat + accu + fin) / fwd, 4))
+
+    # the blend alone: one fixed batch of logits serves every batch of the grid
+    lg = (torch.rand((a.batch, K, h, h), generator=g) * 16 - 8).to(dev)
+    origins = [(int(y), int(x)) for y in ys_h for x in xs_h]
+
+    def blend(kernel):
+        acc, wsum = torch.zeros((K, S, S), device=dev), torch.zeros((S, S), device=dev)
+        e0, e1 = ev(), ev()
+        e0.record()
+        for i0 in starts:
+            n = min(a.batch, total - i0)
+            if kernel:
+                scene_accumulate(lg[:n], ys, xs, i0, wt, acc, wsum)
+            else:
+                for j in range(n):
+                    y, x = origins[i0 + j]
+                    acc[:, y:y + h, x:x + h] += wt * lg[j]
+                    wsum[y:y + h, x:x + h] += wt
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), acc, wsum
+    _, acc_k, wsum_k = blend(True)
+    _, acc_t, wsum_t = blend(False)
+    same = bool(torch.equal(acc_k, acc_t) and torch.equal(wsum_k, wsum_t))
+    tk, tt = [], []
+    for _ in range(a.repeats):                                                 # alternating
+        tk.append(blend(True)[0])
+        tt.append(blend(False)[0])
+    touched = 0
+    for i0 in starts:                                                          # pixels under the union of each launch's windows
+        n = min(a.batch, total - i0)
+        rows = {}
+        for y, x in origins[i0:i0 + n]:
+            rows.setdefault(y, []).append(x)
+        cover = np.zeros((S, S), bool)
+        for y, cols in rows.items():
+            for x in cols:
+                cover[y:y + h, x:x + h] = True
+        touched += int(cover.sum())
+    nbytes = total * K * h * h * 4 + total * h * h * 4 + touched * (K + 1) * 2 * 4
+    emit(what="blend", kernel_ms_median=round(med(tk), 3), torch_slice_loop_ms_median=round(med(tt), 2), torch_over_kernel=round(med(tt) / med(tk), 1),
+         same_bits=same, accumulate_bytes=nbytes, accumulate_tb_per_s=round(nbytes / med(tk) * 1e-9, 3), measured_hbm_tb_per_s=MEASURED_HBM_TBS,
+         launches=len(starts))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
