@@ -756,6 +756,31 @@ int ksmi_scene_accumulate(const float* logits, const int32_t* ys, int ny, const 
  * must be positive everywhere (a grid that covers the scene); 1 <= K <= 8. */
 int ksmi_scene_finalize(const float* acc, const float* wsum, const unsigned char* valid, int K, int64_t HW, int invalid_class,
                         unsigned char* out_class_u8, float* out_score, int score_mode, void* stream);
+/* Minimum mapping unit for the class map of a scene (csrc/sieve.hip; kurosiwo_amd/scene.py: label_components, component_sizes, sieve;
+ * predict.py --mmu).  The reference has no counterpart: it stops at per-tile metrics and never maps a scene.  Integers throughout,
+ * independent of launch geometry and arrival order; tests/sieve_ref.py restates every entry as a flood fill in numpy.  A scene has at
+ * most 2^31 - 1 pixels.  Scratch is the caller's: 4 B of labels, 4 B of sizes and 4 * K B of votes per pixel.
+ *   ksmi_scene_label: the reference has no counterpart.  labels_i32[p] = the smallest linear index y * Ws + x over the pixels of p's
+ *   component, a maximal set of pixels of one class value joined by edges (connectivity 4) or by edges and corners (8); every value
+ *   is labelled.  A fixed number of launches (tile-local union-find in LDS, merges along the tile borders, a flatten pass), nothing
+ *   read on the host.  Hs < 1, Ws < 1, Hs * Ws > 2^31 - 1, another connectivity or a null pointer are KSMI_E_ARG and launch nothing. */
+int ksmi_scene_label(const unsigned char* classes_u8, int Hs, int Ws, int connectivity, int32_t* labels_i32, void* stream);
+/* ksmi_scene_component_sizes: the reference has no counterpart.  sizes_i32 [HW] is zeroed, then sizes_i32[r] = the number of pixels
+ * whose label is r: the component's size at its root index, 0 elsewhere.  HW = 0 is a no-op; HW < 0, HW > 2^31 - 1 or a null pointer
+ * are KSMI_E_ARG.  labels_i32 holds values in [0, HW). */
+int ksmi_scene_component_sizes(const int32_t* labels_i32, int64_t HW, int32_t* sizes_i32, void* stream);
+/* ksmi_scene_sieve_vote: the reference has no counterpart.  A component is small when its size is < mmu and its class is not
+ * invalid; a class value >= K counts as invalid.  For every pixel p of a small component and each of its 4 edge neighbours q inside
+ * the scene (edges whatever the labels' connectivity): votes_i32[class(q)][label(p)] += 1 when q lies in another component that is
+ * neither small nor invalid.  votes_i32 is [K][Hs * Ws]; the K cells at the root of each small component are zeroed first, no other
+ * cell is touched.  1 <= K <= 8; sizes < 1, invalid_class outside 0 .. 255 or a null pointer are KSMI_E_ARG. */
+int ksmi_scene_sieve_vote(const unsigned char* classes_u8, const int32_t* labels_i32, const int32_t* sizes_i32, int mmu, int invalid_class,
+                          int K, int Hs, int Ws, int32_t* votes_i32, void* stream);
+/* ksmi_scene_sieve_apply: the reference has no counterpart.  out_u8[p] = the class with the most votes at label(p) (the lowest class
+ * on a tie) when p's component is small and got a vote, else classes_u8[p]; *removed_i32 += the number of components replaced
+ * (the caller zeroes it).  out_u8 must not alias classes_u8.  HW = 0 is a no-op. */
+int ksmi_scene_sieve_apply(const unsigned char* classes_u8, const int32_t* labels_i32, const int32_t* sizes_i32, const int32_t* votes_i32,
+                           int mmu, int invalid_class, int K, int64_t HW, unsigned char* out_u8, int32_t* removed_i32, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -192,6 +192,10 @@ SIGNATURES = {
     "ksmi_scene_gather": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "ksmi_scene_accumulate": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "ksmi_scene_finalize": (_i, [_vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _i, _vp]),
+    "ksmi_scene_label": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "ksmi_scene_component_sizes": (_i, [_vp, _i64, _vp, _vp]),
+    "ksmi_scene_sieve_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ksmi_scene_sieve_apply": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
     "ksmi_bmm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
     "ksmi_softmax_rows_f32": (_i, [_vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_softmax_rows_backward_f32": (_i, [_vp, _vp, _vp, _i64, _i, C.c_float, _vp]),

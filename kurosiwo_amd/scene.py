@@ -5,7 +5,10 @@ ksmi_scene_gather per input raster cuts and normalises the batch's windows (the 
 under torch.no_grad(), and one ksmi_scene_accumulate adds weight * logits onto the scene in gather form (one thread per scene pixel,
 the covering windows in ascending order, no atomics: the blend is bitwise reproducible and equals the numpy slice loop of
 tests/scene_ref.py).  ksmi_scene_valid marks the pixels where some input is NaN or the nodata sentinel, ksmi_scene_finalize divides
-by the summed weights and takes the first maximum.  Everything runs on the current stream; nothing synchronises."""
+by the summed weights and takes the first maximum.  `sieve` (csrc/sieve.hip) then applies a minimum mapping unit to the class map:
+connected components by a tile-local union-find and border merges, their sizes, and a vote of the large neighbours for every small
+component; integers throughout, equal to the flood fill of tests/sieve_ref.py.  Everything runs on the current stream; nothing
+synchronises."""
 import numpy as np
 import torch
 
@@ -13,6 +16,7 @@ from . import _lib
 from .runtime import require_gpu, stream_ptr
 
 MAX_CLASSES = 8                   # SCENE_MAX_K of csrc/scene.hip
+LABEL_TILE = (16, 64)             # (LT_H, LT_W) of csrc/sieve.hip: the tile one workgroup labels in LDS
 SCORES = {None: None, "logits": 0, "softmax": 1}
 
 
@@ -135,9 +139,73 @@ def scene_finalize(acc, wsum, valid=None, score=None, invalid_class=3):
     return cls, out
 
 
+# ---------------------------------------------------------------------------------------------------- minimum mapping unit
+def _check_map(t, dtype, name, what):
+    require_gpu(t)
+    if t.dtype != dtype or t.dim() != 2 or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} is a contiguous {str(dtype).replace('torch.', '')} device tensor [Hs, Ws]")
+
+
+def label_components(classes, connectivity=4):
+    """ksmi_scene_label: labels int32 [Hs, Ws], labels[p] = the smallest linear index y * Ws + x of p's component (pixels of one class
+    value joined by edges, connectivity 4, or by edges and corners, 8); every class value is labelled"""
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity is 4 or 8, got {connectivity!r}")
+    _check_map(classes, torch.uint8, "label_components", "classes")
+    Hs, Ws = classes.shape
+    labels = torch.empty((Hs, Ws), dtype=torch.int32, device=classes.device)
+    if Hs * Ws:
+        _lib.check(_lib.load().ksmi_scene_label(classes.data_ptr(), Hs, Ws, int(connectivity), labels.data_ptr(), stream_ptr()), "scene_label")
+    return labels
+
+
+def component_sizes(labels):
+    """ksmi_scene_component_sizes: sizes int32 [Hs, Ws], at a root index (labels[p] == p) the pixels of that component, 0 elsewhere"""
+    _check_map(labels, torch.int32, "component_sizes", "labels")
+    sizes = torch.empty_like(labels)
+    _lib.check(_lib.load().ksmi_scene_component_sizes(labels.data_ptr(), labels.numel(), sizes.data_ptr(), stream_ptr()), "scene_component_sizes")
+    return sizes
+
+
+def sieve(classes, mmu, connectivity=4, invalid_class=3, num_classes=4, passes=1):
+    """Minimum mapping unit -> (classes uint8 [Hs, Ws], removed int32 device tensor [1]).
+
+    One pass, judged on its input map alone: a component (label_components at `connectivity`) is small when it has fewer than `mmu`
+    pixels and its class is not `invalid_class`.  Every pixel of a small component lets each of its 4 edge neighbours inside the scene
+    vote for its class when that neighbour lies in another component that is neither small nor invalid; the component takes the class
+    with the most votes (the lowest class on a tie) or, without a vote, keeps its own.  The invalid class (and any value >=
+    num_classes) is never changed and never votes; mmu <= 1 is the identity.  passes = n repeats the pass on its own output; removed
+    counts the components replaced over all passes.  The input is left alone.  Scratch: 8 + 4 * num_classes bytes per pixel."""
+    if connectivity not in (4, 8):
+        raise ValueError(f"sieve: connectivity is 4 or 8, got {connectivity!r}")
+    if not 1 <= int(num_classes) <= MAX_CLASSES:
+        raise ValueError(f"sieve: 1 <= num_classes <= {MAX_CLASSES}, got {num_classes!r}")
+    if int(passes) < 1:
+        raise ValueError(f"sieve: passes >= 1, got {passes!r}")
+    if not 0 <= int(invalid_class) <= 255:
+        raise ValueError(f"sieve: invalid_class in 0 .. 255, got {invalid_class!r}")
+    _check_map(classes, torch.uint8, "sieve", "classes")
+    mmu, K, Hs, Ws = int(mmu), int(num_classes), classes.shape[0], classes.shape[1]
+    removed = torch.zeros(1, dtype=torch.int32, device=classes.device)
+    if mmu <= 1 or Hs * Ws == 0:
+        return classes.clone(), removed
+    lib, st = _lib.load(), stream_ptr()
+    votes = torch.empty((K, Hs, Ws), dtype=torch.int32, device=classes.device)       # only the cells at small roots are ever used
+    for _ in range(int(passes)):
+        labels = label_components(classes, connectivity)
+        sizes = component_sizes(labels)
+        out = torch.empty_like(classes)
+        _lib.check(lib.ksmi_scene_sieve_vote(classes.data_ptr(), labels.data_ptr(), sizes.data_ptr(), mmu, int(invalid_class), K, Hs, Ws,
+                                             votes.data_ptr(), st), "scene_sieve_vote")
+        _lib.check(lib.ksmi_scene_sieve_apply(classes.data_ptr(), labels.data_ptr(), sizes.data_ptr(), votes.data_ptr(), mmu, int(invalid_class),
+                                              K, Hs * Ws, out.data_ptr(), removed.data_ptr(), st), "scene_sieve_apply")
+        classes = out
+    return classes, removed
+
+
 # ---------------------------------------------------------------------------------------------------- the scene loop
 def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, weight="hann", nodata=None, score=None, raw=False,
-                  invalid_class=3):
+                  invalid_class=3, mmu=None, connectivity=4):
     """A class map of a whole scene.
 
     rasters: device float32 [C_i, Hs, Ws], one per model input (e.g. pre, post, DEM), all of one size.
@@ -148,9 +216,13 @@ def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, wei
     nodata:  the sentinel of the rasters (None: only NaN is missing); one value, or one per raster.
     raw:     gather raw values (nodata -> NaN) for a model that normalises inside its first convolution (cd_forward(..., norms)).
     score:   None, "logits" (the blended mean logits) or "softmax".
+    mmu:     None, or the minimum mapping unit in pixels: the class map goes through one pass of `sieve` at `connectivity` (4 or 8)
+             over the model's K classes.  The scores are returned unchanged: they describe the blend, not the sieved map.
     Returns (classes uint8 [Hs, Ws] with `invalid_class` where some input is missing, scores float32 [K, Hs, Ws] or None)."""
     if score not in SCORES:
         raise ValueError(f'predict_scene: score is None, "logits" or "softmax", got {score!r}')
+    if mmu is not None and connectivity not in (4, 8):
+        raise ValueError(f"predict_scene: connectivity is 4 or 8, got {connectivity!r}")
     if not rasters or len(norms) != len(rasters):
         raise ValueError("predict_scene: one (mean, std, clamp) per raster")
     for r in rasters:
@@ -191,7 +263,10 @@ def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, wei
         valid = None
         for r, nd in zip(rasters, nodatas):
             valid = scene_valid(r, nd, valid)
-        return scene_finalize(acc, wsum, valid, score, invalid_class)
+        classes, scores = scene_finalize(acc, wsum, valid, score, invalid_class)
+        if mmu is not None:
+            classes, _ = sieve(classes, mmu, connectivity, invalid_class, acc.shape[0])
+        return classes, scores
 
 
 # ---------------------------------------------------------------------------------------------------- model adapters

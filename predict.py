@@ -4,15 +4,24 @@
   python predict.py --task cd --method snunet --checkpoint best.pt \\
       --post VV.tif VH.tif --pre1 VV.tif VH.tif [--pre2 ...] [--dem dem.tif] \\
       --out flood.tif [--score softmax --score_out prob.tif] \\
-      [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16]
+      [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] \\
+      [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
 nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
 ("Invalid pixels").  The DEM's gaps are filled on the host as the loaders fill them, and the DEM is standardised with the loaders'
 constants.  The class raster is a Deflate-compressed uint8 GeoTIFF in tiles of 256 with the first post file's georeferencing and
 nodata = 3; the scores, where asked for, a float32 multi-band file written the same way.  The scene, the accumulators and the outputs
-live on one device: a scene that does not fit is outside this tool, as are --slope, SLC products and test-time flips."""
+live on one device: a scene that does not fit is outside this tool, as are --slope, SLC products and test-time flips.
+
+--mmu N applies a minimum mapping unit on the device before the map is written (kurosiwo_amd.scene.sieve): every connected component
+(--connectivity 4: joined by edges, 8: by edges and corners) of fewer than N pixels takes the class most of its edge neighbours in
+components of at least N pixels have; invalid pixels are never changed and never vote; --sieve_passes repeats the pass on its own
+output.  The scores of --score_out describe the blend, not the sieved map.  --report FILE.json writes what the map holds, counted on
+the class map as written: "pixel_counts" per class 0 .. 3, "pixel_area" (the product of the first post file's pixel scale, in map
+units squared; null without georeferencing), "class_area" per class, "mmu", "connectivity", "passes" and "components_removed"."""
 import argparse
+import json
 import os
 import sys
 from types import SimpleNamespace
@@ -27,7 +36,7 @@ if ROOT not in sys.path:
 from kurosiwo_amd import geotiff                                            # noqa: E402
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
-from kurosiwo_amd.scene import cd_forward, predict_scene, seg_forward       # noqa: E402
+from kurosiwo_amd.scene import cd_forward, predict_scene, seg_forward, sieve                      # noqa: E402
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -52,6 +61,10 @@ parser.add_argument("--batch_size", type=int, default=32)
 parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
 parser.add_argument("--raw", action="store_true", default=False,
                     help="hand raw windows to a model that normalises inside its first convolution (snunet)")
+parser.add_argument("--mmu", type=int, default=None, help="minimum mapping unit in pixels: smaller components take their neighbours' class")
+parser.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
+parser.add_argument("--sieve_passes", type=int, default=1)
+parser.add_argument("--report", default=None, help="FILE.json: per-class pixel counts and areas of the map as written")
 
 
 def read_date(paths, nodata):
@@ -99,6 +112,8 @@ def main(argv=None):
         raise SystemExit("predict.py: --slope is not supported: the slope of a whole scene is not computed here (train and map with --dem)")
     if (args.score is None) != (args.score_out is None):
         raise SystemExit("predict.py: --score and --score_out come together")
+    if args.sieve_passes < 1:
+        raise SystemExit("predict.py: --sieve_passes >= 1")
     method = args.method.lower()
     task = args.task or ("cd" if method in CD_METHODS else "segmentation")
     dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
@@ -149,9 +164,25 @@ def main(argv=None):
     classes, score = predict_scene(forward, [torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in rasters], norms, window=args.window,
                                    stride=args.stride, batch=args.batch_size, weight=args.weight, nodata=nodatas, score=args.score,
                                    raw=args.raw)
+    removed = 0
+    if args.mmu is not None:                            # class 3 is the invalid class of the map: a vote table of at least 4 rows
+        classes, gone = sieve(classes, args.mmu, args.connectivity, invalid_class=3, num_classes=max(4, int(configs["num_classes"])),
+                              passes=args.sieve_passes)
+        removed = int(gone.item())
     where = dict(compression="deflate", tile=(256, 256), pixel_scale=geo["pixel_scale"], origin=geo["origin"])
-    geotiff.write(args.out, classes.cpu().numpy(), nodata=3, **where)
-    print(f"wrote {args.out}: {classes.shape[0]} x {classes.shape[1]} classes")
+    written = classes.cpu().numpy()
+    geotiff.write(args.out, written, nodata=3, **where)
+    print(f"wrote {args.out}: {classes.shape[0]} x {classes.shape[1]} classes" + (
+        f", {removed} components below {args.mmu} pixels removed" if args.mmu is not None else ""))
+    if args.report is not None:
+        counts = np.bincount(written.ravel(), minlength=4).tolist()
+        scale = geo["pixel_scale"]
+        area = None if scale is None else float(scale[0]) * float(scale[1])
+        with open(args.report, "w") as f:
+            json.dump({"pixel_counts": counts, "pixel_area": area, "class_area": None if area is None else [area * c for c in counts],
+                       "mmu": args.mmu, "connectivity": args.connectivity, "passes": args.sieve_passes, "components_removed": removed}, f,
+                      indent=1)
+        print(f"wrote {args.report}")
     if score is not None:
         geotiff.write(args.score_out, score.cpu().numpy(), nodata=float("nan"), **where)
         print(f"wrote {args.score_out}: {score.shape[0]} bands of {args.score}")

@@ -1,6 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
+                                [--mmu N [--connectivity 4] [--sieve_only]]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -11,6 +12,12 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              sums written as the torch slice loop on the device (acc[:, y:y+h, x:x+w] += weight * logits[i]; wsum[...] += weight)
   bytes/s    of the accumulate launches: logits read once, weight read per window cell, acc and wsum read and written once per touched
              pixel per launch (counted from the grid), over their summed event time; next to the measured HBM rate the README quotes
+  sieve      with --mmu N (the numbers behind profiles/sieve_probe.txt): one pass of the minimum mapping unit on a size x size class map
+             of three contents -- one class everywhere (a single component: the contended count), speckle_scene of tests/sieve_ref.py,
+             a one-pixel checkerboard (at 4-connectivity every pixel its own component) -- as the event time of each entry point:
+             ksmi_scene_label (3 launches), ksmi_scene_component_sizes (memset + 1), ksmi_scene_sieve_vote (2), ksmi_scene_sieve_apply
+             (1), and their sum; where scipy is installed, scipy.ndimage.label per class on the host for the same map.  --sieve_only
+             skips the model passes above.
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -32,6 +39,9 @@ def main():
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--mmu", type=int, default=None)
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
+    ap.add_argument("--sieve_only", action="store_true", default=False)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -41,6 +51,25 @@ def main():
     from kurosiwo_amd.snunet import SNUNet_ECAM
     if not torch.cuda.is_available():
         raise SystemExit("scene_probe: no GPU: nothing here can be measured on the host")
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    med = statistics.median
+    lines = []
+
+    def emit(**kv):
+        line = json.dumps(kv)
+        print(line, flush=True)
+        lines.append(line)
+
+    def finish():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+
+    if a.mmu is not None:
+        sieve_probe(a, emit, ev, med)
+        if a.sieve_only:
+            return finish()
     data = load_json5(os.path.join(HERE, "configs", "train", "data_config.json"))
     norm = (data["data_mean"], data["data_std"], [data["clamp_input"]] * 2)
     dev, S, h, K = torch.device("cuda"), a.size, a.window, 3
@@ -59,14 +88,6 @@ def main():
     ys, xs = torch.from_numpy(ys_h).to(dev), torch.from_numpy(xs_h).to(dev)
     wt = torch.from_numpy(blend_weights(h, h, "hann")).to(dev)
     dev_norm = tuple(torch.tensor(v, dtype=torch.float32, device=dev) for v in norm)
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    med = statistics.median
-    lines = []
-
-    def emit(**kv):
-        line = json.dumps(kv)
-        print(line, flush=True)
-        lines.append(line)
 
     def whole():
         e0, e1 = ev(), ev()
@@ -155,10 +176,64 @@ def main():
     emit(what="blend", kernel_ms_median=round(med(tk), 3), torch_slice_loop_ms_median=round(med(tt), 2), torch_over_kernel=round(med(tt) / med(tk), 1),
          same_bits=same, accumulate_bytes=nbytes, accumulate_tb_per_s=round(nbytes / med(tk) * 1e-9, 3), measured_hbm_tb_per_s=MEASURED_HBM_TBS,
          launches=len(starts))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+    finish()
+
+
+def sieve_probe(a, emit, ev, med):
+    """one pass of the sieve on three maps of a.size x a.size, timed per entry point"""
+    import time
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib
+    from kurosiwo_amd.runtime import stream_ptr
+    from kurosiwo_amd.scene import component_sizes, label_components
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    try:
+        from scipy import ndimage
+    except ImportError:
+        ndimage = None
+    S, K, mmu, conn, lib, st = a.size, 4, a.mmu, a.connectivity, _lib.load(), stream_ptr()
+    yy, xx = np.mgrid[0:S, 0:S]
+    maps = {"one_class": np.zeros((S, S), np.uint8), "speckle": sieve_ref.speckle_scene(4480, S, S), "checkerboard": ((yy + xx) & 1).astype(np.uint8)}
+    del yy, xx
+    votes = torch.empty((K, S, S), dtype=torch.int32, device="cuda")
+    for name, m in maps.items():
+        d = torch.from_numpy(m).cuda()
+        out, removed = torch.empty_like(d), torch.zeros(1, dtype=torch.int32, device="cuda")
+        ptr = lambda t: t.data_ptr()
+
+        def one_pass():
+            e = [ev() for _ in range(5)]
+            removed.zero_()
+            e[0].record()
+            lab = label_components(d, conn)
+            e[1].record()
+            size = component_sizes(lab)
+            e[2].record()
+            _lib.check(lib.ksmi_scene_sieve_vote(ptr(d), ptr(lab), ptr(size), mmu, 3, K, S, S, ptr(votes), st), "scene_sieve_vote")
+            e[3].record()
+            _lib.check(lib.ksmi_scene_sieve_apply(ptr(d), ptr(lab), ptr(size), ptr(votes), mmu, 3, K, S * S, ptr(out), ptr(removed), st),
+                       "scene_sieve_apply")
+            e[4].record()
+            torch.cuda.synchronize()
+            return [e[j].elapsed_time(e[j + 1]) for j in range(4)], lab, size
+        _, lab, size = one_pass()                                              # warm-up
+        components = int((size > 0).sum())
+        first = (lab.clone(), out.clone(), int(removed.item()))
+        runs = [one_pass() for _ in range(a.repeats)]
+        assert torch.equal(runs[-1][1], first[0]) and torch.equal(out, first[1]) and int(removed.item()) == first[2]      # equal bits
+        t = [med(r[0][j] for r in runs) for j in range(4)]
+        host = None
+        if ndimage is not None:
+            structure = np.ones((3, 3), int) if conn == 8 else None
+            t0 = time.perf_counter()
+            n = sum(ndimage.label(m == c, structure)[1] for c in np.unique(m))
+            host = round((time.perf_counter() - t0) * 1e3, 1)
+            assert n == components
+        emit(what="sieve", content=name, size=S, mmu=mmu, connectivity=conn, components=components, removed=first[2],
+             label_ms=round(t[0], 3), sizes_ms=round(t[1], 3), vote_ms=round(t[2], 3), apply_ms=round(t[3], 3), total_ms=round(sum(t), 3),
+             mpixels_per_s=round(S * S / sum(t) * 1e-3, 1), scipy_label_host_ms=host)
 
 
 if __name__ == "__main__":
