@@ -781,6 +781,66 @@ int ksmi_scene_sieve_vote(const unsigned char* classes_u8, const int32_t* labels
  * (the caller zeroes it).  out_u8 must not alias classes_u8.  HW = 0 is a no-op. */
 int ksmi_scene_sieve_apply(const unsigned char* classes_u8, const int32_t* labels_i32, const int32_t* sizes_i32, const int32_t* votes_i32,
                            int mmu, int invalid_class, int K, int64_t HW, unsigned char* out_u8, int32_t* removed_i32, void* stream);
+/* Polygon output for the class map of a scene (csrc/polygon.hip; kurosiwo_amd/scene.py: scan_i32, boundary_edges, trace_rings,
+ * polygonize; predict.py --polygons).  The reference has no counterpart.  Integers throughout, independent of launch geometry and
+ * arrival order; tests/polygon_ref.py restates every entry as a sequential boundary walk.  Image coordinates: x right, y down, a
+ * vertex is a pixel corner.  Side s of pixel p = y * Ws + x is walked clockwise on screen (0 top, 1 right, 2 bottom, 3 left; the pixel
+ * on the right of the heading); it is a boundary edge when p's class is selected and the pixel across it is outside the scene or has
+ * another label; edge id 4 * p + s; compact index = rank among all boundary edges by edge id.  Bit c of select_mask selects class c,
+ * 0 <= c <= 62 (a negative mask is KSMI_E_ARG).  labels_i32 are the 4-connectivity labels of ksmi_scene_label.  A scene to polygonise
+ * has at most 2^29 - 1 pixels, so that every edge id and E fit int32.  Scratch is the caller's.  Every entry: a size of 0 is a no-op
+ * that returns 0; a negative size, a size past its bound or a null pointer are KSMI_E_ARG and launch nothing.  Indices read from the
+ * caller's arrays are checked before they address anything: arrays that describe no rings give meaningless numbers, nothing worse.
+ *   ksmi_scan_i32_scratch: the int32 elements of scratch ksmi_scan_i32 needs for n elements (0 for n <= 2048, one tile); -1 for
+ *   n < 0 or n > 2^31 - 1. */
+int64_t ksmi_scan_i32_scratch(int64_t n);
+/* ksmi_scan_i32: replaces torch.cumsum, which has no exclusive form and would need an int64 copy.  out_i32[i] = in_i32[0] + ... +
+ * in_i32[i - 1], *total_i64 = the sum of all n, n <= 2^31 - 1.  Three passes: sums of tiles of 2048 elements (one workgroup each), the
+ * scan of those sums (the same passes again, as deep as n needs), the scan of each tile from its offset.  out_i32 may alias in_i32.
+ * The caller guarantees that every prefix and the total fit int32.  scratch_elems < ksmi_scan_i32_scratch of n is KSMI_E_ARG. */
+int ksmi_scan_i32(const int32_t* in_i32, int32_t* out_i32, int64_t n, int64_t* total_i64, int32_t* scratch_i32, int64_t scratch_elems,
+                  void* stream);
+/* ksmi_scene_edge_count: counts_i32[p] = the boundary edges of pixel p, 0 .. 4 (0 where p's class is not selected).  Its exclusive
+ * scan gives every pixel the compact index of its first edge, and E. */
+int ksmi_scene_edge_count(const unsigned char* classes_u8, const int32_t* labels_i32, int64_t select_mask, int Hs, int Ws, int32_t* counts_i32,
+                          void* stream);
+/* ksmi_scene_edge_emit: offsets_i32 = the scanned counts.  For each boundary edge, at its compact index k: eid_i32[k] = its edge id,
+ * succ_i32[k] = the compact index of its successor.  The edge ends at vertex v with heading s; L = the pixel ahead-left of v, R = the
+ * pixel ahead-right: the successor is side s - 1 of L when label(L) == label(p) (turn left), else side s of R when label(R) ==
+ * label(p) (straight on), else side s + 1 of p (turn right); sides modulo 4.  At a corner where two diagonal pixels of one component
+ * meet the walk crosses to the diagonal pixel.  The successor map is a permutation of the boundary edges; its cycles are the rings.
+ * E outside 0 .. 4 * Hs * Ws is KSMI_E_ARG; an edge whose index is not below E is not written. */
+int ksmi_scene_edge_emit(const unsigned char* classes_u8, const int32_t* labels_i32, int64_t select_mask, int Hs, int Ws,
+                         const int32_t* offsets_i32, int64_t E, int32_t* eid_i32, int32_t* succ_i32, void* stream);
+/* ksmi_scene_ring_trace: pointer doubling over succ_i32 [E], double-buffered in scratch_i32 (4 * E elements; fewer is KSMI_E_ARG),
+ * ceil(log2(E)) rounds per phase whatever the rings look like: nothing is read back.  ring_min_i32[k] = the smallest compact index
+ * on k's ring; rank_i32[k] = the successor steps from that smallest edge to k (0 at the smallest edge; the edge whose successor is the
+ * smallest edge has the ring's length - 1).  phases: 3 runs both; 1 only the first (rank_i32 may be NULL); 2 only the second, reading
+ * the ring_min_i32 of an earlier call; another value is KSMI_E_ARG. */
+int ksmi_scene_ring_trace(const int32_t* succ_i32, int64_t E, int phases, int32_t* ring_min_i32, int32_t* rank_i32, int32_t* scratch_i32,
+                          int64_t scratch_elems, void* stream);
+/* ksmi_scene_ring_heads: flags_i32[k] = 1 where ring_min_i32[k] == k, else 0.  Its exclusive scan numbers the rings in ascending ring
+ * id (the edge id of a ring's smallest edge) without a sort, and gives R. */
+int ksmi_scene_ring_heads(const int32_t* ring_min_i32, int64_t E, int32_t* flags_i32, void* stream);
+/* ksmi_scene_ring_table: ring_index_i32 = the scanned head flags.  Per ring r: ring_id_i32[r] = the edge id of its smallest edge,
+ * label_i32[r] = the label of that edge's pixel, length_i32[r] = its edges.  The exclusive scan of the lengths is each ring's offset in
+ * ring order. */
+int ksmi_scene_ring_table(const int32_t* eid_i32, const int32_t* succ_i32, const int32_t* ring_min_i32, const int32_t* rank_i32,
+                          const int32_t* ring_index_i32, const int32_t* labels_i32, int64_t HW, int64_t E, int64_t R, int32_t* ring_id_i32,
+                          int32_t* label_i32, int32_t* length_i32, void* stream);
+/* ksmi_scene_ring_order: the edges in ring order.  At position ring_offset_i32[ring of k] + rank_i32[k]: ordered_eid_i32 = k's edge
+ * id, ordered_ring_i32 = its ring number, turn_i32 = 1 when k's successor has another side number (the walk turns at k's end vertex),
+ * else 0.  The exclusive scan of the turn flags is each vertex's place, and gives V. */
+int ksmi_scene_ring_order(const int32_t* eid_i32, const int32_t* succ_i32, const int32_t* ring_min_i32, const int32_t* rank_i32,
+                          const int32_t* ring_index_i32, const int32_t* ring_offset_i32, int64_t E, int64_t R, int32_t* ordered_eid_i32,
+                          int32_t* ordered_ring_i32, int32_t* turn_i32, void* stream);
+/* ksmi_scene_ring_verts: vertex_offset_i32 = the scanned turn flags.  verts_i32 [V][2] = (x, y) of the end vertex of every turning
+ * edge, in ring order (collinear vertices are dropped); start_i32 [R + 1] = the first vertex of each ring, start_i32[R] = V;
+ * area2_i64 [R] (zeroed here) = the sum over the ring's edges of x0 * y1 - x1 * y0: positive for the one exterior ring of a component,
+ * negative for its holes, and over a component twice its pixel count.  The terms of one ring are combined per wave and per
+ * workgroup before the global integer add. */
+int ksmi_scene_ring_verts(const int32_t* ordered_eid_i32, const int32_t* ordered_ring_i32, const int32_t* vertex_offset_i32, int64_t E,
+                          int64_t R, int64_t V, int Ws, int32_t* verts_i32, int32_t* start_i32, int64_t* area2_i64, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

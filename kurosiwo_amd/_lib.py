@@ -196,6 +196,15 @@ SIGNATURES = {
     "ksmi_scene_component_sizes": (_i, [_vp, _i64, _vp, _vp]),
     "ksmi_scene_sieve_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ksmi_scene_sieve_apply": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp, _vp]),
+    "ksmi_scan_i32_scratch": (_i64, [_i64]),
+    "ksmi_scan_i32": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "ksmi_scene_edge_count": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "ksmi_scene_edge_emit": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _vp]),
+    "ksmi_scene_ring_trace": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _i64, _vp]),
+    "ksmi_scene_ring_heads": (_i, [_vp, _i64, _vp, _vp]),
+    "ksmi_scene_ring_table": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ksmi_scene_ring_order": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ksmi_scene_ring_verts": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "ksmi_bmm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
     "ksmi_softmax_rows_f32": (_i, [_vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_softmax_rows_backward_f32": (_i, [_vp, _vp, _vp, _i64, _i, C.c_float, _vp]),

@@ -7,8 +7,13 @@ the covering windows in ascending order, no atomics: the blend is bitwise reprod
 tests/scene_ref.py).  ksmi_scene_valid marks the pixels where some input is NaN or the nodata sentinel, ksmi_scene_finalize divides
 by the summed weights and takes the first maximum.  `sieve` (csrc/sieve.hip) then applies a minimum mapping unit to the class map:
 connected components by a tile-local union-find and border merges, their sizes, and a vote of the large neighbours for every small
-component; integers throughout, equal to the flood fill of tests/sieve_ref.py.  Everything runs on the current stream; nothing
-synchronises."""
+component; integers throughout, equal to the flood fill of tests/sieve_ref.py.  `polygonize` (csrc/polygon.hip) turns the class map
+into boundary rings: the boundary edges of the 4-connected components, each with its successor, the rings by pointer doubling, and the
+vertex lists in ring order; `polygons_geojson` writes them as GeoJSON on the host.  Everything runs on the current stream; nothing
+synchronises but the three counts (edges, rings, vertices) that `polygonize` reads to size its buffers."""
+import gc
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -17,6 +22,9 @@ from .runtime import require_gpu, stream_ptr
 
 MAX_CLASSES = 8                   # SCENE_MAX_K of csrc/scene.hip
 LABEL_TILE = (16, 64)             # (LT_H, LT_W) of csrc/sieve.hip: the tile one workgroup labels in LDS
+SCAN_TILE = 2048                  # SCAN_TILE of csrc/polygon.hip: the elements one workgroup scans
+MAX_POLYGON_PIXELS = 2 ** 29 - 1  # edge ids 4 * p + s and the edge count fit int32
+Rings = namedtuple("Rings", "label ring_id start area2 verts")
 SCORES = {None: None, "logits": 0, "softmax": 1}
 
 
@@ -201,6 +209,202 @@ def sieve(classes, mmu, connectivity=4, invalid_class=3, num_classes=4, passes=1
                                               K, Hs * Ws, out.data_ptr(), removed.data_ptr(), st), "scene_sieve_apply")
         classes = out
     return classes, removed
+
+
+# ---------------------------------------------------------------------------------------------------- polygon output
+def _check_vec(t, name, what, dtype=torch.int32):
+    require_gpu(t)
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f"{name}: {what} is a contiguous {str(dtype).replace('torch.', '')} device vector")
+
+
+def _select_mask(select, name):
+    mask = 0
+    for c in select:
+        if int(c) != c or not 0 <= int(c) <= 62:
+            raise ValueError(f"{name}: select holds class values 0 .. 62, got {c!r}")
+        mask |= 1 << int(c)
+    return mask
+
+
+def _scan(x, out, name):
+    """exclusive scan of the int32 device vector x into out (x itself: in place) -> the total, an int64 device tensor [1]"""
+    n = x.numel()
+    total = torch.zeros(1, dtype=torch.int64, device=x.device)
+    if n:
+        lib = _lib.load()
+        need = int(lib.ksmi_scan_i32_scratch(n))
+        scratch = torch.empty(max(need, 1), dtype=torch.int32, device=x.device)
+        _lib.check(lib.ksmi_scan_i32(x.data_ptr(), out.data_ptr(), n, total.data_ptr(), scratch.data_ptr(), need, stream_ptr()), name)
+    return total
+
+
+def scan_i32(x, out=None):
+    """ksmi_scan_i32 -> (prefix int32 [n], total int64 device tensor [1]): prefix[i] = x[0] + ... + x[i - 1], total = the sum of all.
+    Every prefix and the total must fit int32.  out: where the prefix goes (x itself: in place); by default a new tensor, and x is
+    left alone.  Tiles of SCAN_TILE elements, three passes, as deep as n needs."""
+    _check_vec(x, "scan_i32", "x")
+    if x.numel() > 2 ** 31 - 1:
+        raise ValueError("scan_i32: at most 2^31 - 1 elements")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check_vec(out, "scan_i32", "out")
+        if out.shape != x.shape or out.device != x.device:
+            raise ValueError("scan_i32: out has the length and the device of x")
+    return out, _scan(x, out, "scan_i32")
+
+
+def _check_polygon_maps(classes, labels, name):
+    _check_map(classes, torch.uint8, name, "classes")
+    if labels is not None:
+        _check_map(labels, torch.int32, name, "labels")
+        if labels.shape != classes.shape or labels.device != classes.device:
+            raise ValueError(f"{name}: labels has the shape and the device of classes")
+    if classes.numel() > MAX_POLYGON_PIXELS:
+        raise ValueError(f"{name}: at most 2^29 - 1 pixels (edge ids are int32), got {classes.numel()}")
+
+
+def _boundary_edges(classes, labels, mask):
+    """(eid, succ, E) -- two host-visible launches around one scan; E is the one value read back"""
+    Hs, Ws = classes.shape
+    dev = classes.device
+    lib, st = _lib.load(), stream_ptr()
+    empty = lambda: torch.empty(0, dtype=torch.int32, device=dev)
+    if Hs * Ws == 0:
+        return empty(), empty(), 0
+    offsets = torch.empty(Hs * Ws, dtype=torch.int32, device=dev)
+    _lib.check(lib.ksmi_scene_edge_count(classes.data_ptr(), labels.data_ptr(), mask, Hs, Ws, offsets.data_ptr(), st), "scene_edge_count")
+    E = int(_scan(offsets, offsets, "scan_i32").item())             # the first of the three host reads
+    if E == 0:
+        return empty(), empty(), 0
+    eid, succ = torch.empty(E, dtype=torch.int32, device=dev), torch.empty(E, dtype=torch.int32, device=dev)
+    _lib.check(lib.ksmi_scene_edge_emit(classes.data_ptr(), labels.data_ptr(), mask, Hs, Ws, offsets.data_ptr(), E, eid.data_ptr(),
+                                        succ.data_ptr(), st), "scene_edge_emit")
+    return eid, succ, E
+
+
+def boundary_edges(classes, labels, select=(1, 2)):
+    """ksmi_scene_edge_count, ksmi_scan_i32, ksmi_scene_edge_emit -> (eid int32 [E], succ int32 [E]).
+
+    Side s of pixel p = y * Ws + x (0 top, 1 right, 2 bottom, 3 left, walked clockwise on screen with the pixel on the right) is a
+    boundary edge when p's class is in `select` (values 0 .. 62) and the pixel across it is outside the scene or has another label.
+    eid[k] = 4 * p + s in ascending order; succ[k] = the index of the next edge of the ring: at the edge's end, turn left when the pixel
+    ahead-left has p's label, else go straight when the pixel ahead-right has it, else turn right around p.  labels: the
+    4-connectivity labels of label_components(classes, 4)."""
+    mask = _select_mask(select, "boundary_edges")
+    _check_polygon_maps(classes, labels, "boundary_edges")
+    if labels is None:
+        raise ValueError("boundary_edges: labels is the int32 map of label_components(classes, 4)")
+    eid, succ, _ = _boundary_edges(classes, labels, mask)
+    return eid, succ
+
+
+def trace_rings(succ):
+    """ksmi_scene_ring_trace -> (ring_min int32 [E], rank int32 [E]): for a permutation succ, the smallest index on k's cycle and the
+    number of successor steps from it to k.  Pointer doubling, 2 * ceil(log2(E)) rounds whatever the rings look like; 16 B of scratch
+    per edge."""
+    _check_vec(succ, "trace_rings", "succ")
+    E = succ.numel()
+    if E > 2 ** 31 - 1:
+        raise ValueError("trace_rings: at most 2^31 - 1 edges")
+    ring_min, rank = torch.empty_like(succ), torch.empty_like(succ)
+    if E:
+        scratch = torch.empty(4 * E, dtype=torch.int32, device=succ.device)
+        _lib.check(_lib.load().ksmi_scene_ring_trace(succ.data_ptr(), E, 3, ring_min.data_ptr(), rank.data_ptr(), scratch.data_ptr(), 4 * E,
+                                                     stream_ptr()), "scene_ring_trace")
+    return ring_min, rank
+
+
+def polygonize(classes, select=(1, 2), labels=None):
+    """The boundary rings of a class map -> Rings(label, ring_id, start, area2, verts), device tensors.
+
+    One ring per boundary of every 4-connected component whose class is in `select` (values 0 .. 62), in ascending ring id:
+      label   int32 [R]      the component: the smallest linear index y * Ws + x of its pixels (label_components(classes, 4))
+      ring_id int32 [R]      the smallest edge id 4 * p + s of the ring; a component's exterior ring has id 4 * label, its smallest
+      start   int32 [R + 1]  ring r has the vertices verts[start[r]:start[r + 1]]
+      area2   int64 [R]      the sum of x0 * y1 - x1 * y0 over the ring's edges: positive for the exterior ring, negative for a hole;
+                             over a component twice its pixel count
+      verts   int32 [V, 2]   (x, y) pixel corners, x right and y down, clockwise on screen around the component (holes the other way),
+                             collinear vertices dropped, the first vertex not repeated
+    Nothing selected: empty tensors and start == [0].  labels, if given, must be the 4-connectivity labels of `classes`
+    (label_components(classes, 4)): with 8-connectivity labels a ring would touch itself at corners.  At most 2^29 - 1 pixels.  Three
+    integers are read on the host (edges, rings, vertices) to size the buffers; scratch: 8 B per pixel and 48 B per boundary edge."""
+    mask = _select_mask(select, "polygonize")
+    _check_polygon_maps(classes, labels, "polygonize")
+    Hs, Ws = classes.shape
+    dev = classes.device
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    if labels is None and Hs * Ws:
+        labels = label_components(classes, 4)
+    eid, succ, E = _boundary_edges(classes, labels, mask)
+    if E == 0:
+        return Rings(i32(0), i32(0), torch.zeros(1, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                     torch.empty((0, 2), dtype=torch.int32, device=dev))
+    lib, st = _lib.load(), stream_ptr()
+    ring_min, rank = trace_rings(succ)
+    ring_index = i32(E)
+    _lib.check(lib.ksmi_scene_ring_heads(ring_min.data_ptr(), E, ring_index.data_ptr(), st), "scene_ring_heads")
+    R = int(_scan(ring_index, ring_index, "scan_i32").item())           # the second host read
+    ring_id, label, offset = i32(R), i32(R), i32(R)
+    _lib.check(lib.ksmi_scene_ring_table(eid.data_ptr(), succ.data_ptr(), ring_min.data_ptr(), rank.data_ptr(), ring_index.data_ptr(),
+                                         labels.data_ptr(), Hs * Ws, E, R, ring_id.data_ptr(), label.data_ptr(), offset.data_ptr(), st),
+               "scene_ring_table")
+    _scan(offset, offset, "scan_i32")                                   # lengths -> offsets in ring order; the total is E
+    ordered_eid, ordered_ring, vertex_offset = i32(E), i32(E), i32(E)
+    _lib.check(lib.ksmi_scene_ring_order(eid.data_ptr(), succ.data_ptr(), ring_min.data_ptr(), rank.data_ptr(), ring_index.data_ptr(),
+                                         offset.data_ptr(), E, R, ordered_eid.data_ptr(), ordered_ring.data_ptr(), vertex_offset.data_ptr(), st),
+               "scene_ring_order")
+    V = int(_scan(vertex_offset, vertex_offset, "scan_i32").item())     # the third
+    verts = torch.empty((V, 2), dtype=torch.int32, device=dev)
+    start = i32(R + 1)
+    area2 = torch.empty(R, dtype=torch.int64, device=dev)
+    _lib.check(lib.ksmi_scene_ring_verts(ordered_eid.data_ptr(), ordered_ring.data_ptr(), vertex_offset.data_ptr(), E, R, V, Ws,
+                                         verts.data_ptr(), start.data_ptr(), area2.data_ptr(), st), "scene_ring_verts")
+    return Rings(label, ring_id, start, area2, verts)
+
+
+def polygons_geojson(rings, classes, pixel_scale=None, origin=None):
+    """A GeoJSON FeatureCollection (a dict) of the rings of `polygonize`, built on the host.
+
+    One Polygon feature per component in ascending label: its exterior ring first, then its holes in ascending ring id, each closed by
+    repeating its first vertex.  Coordinates are [ox + x * sx, oy - y * sy] in float64 with pixel_scale = (sx, sy) and origin = (ox, oy)
+    as geotiff.read returns them (the model position of the corner of pixel (0, 0)); without georeferencing the scale is (1, 1) and
+    the origin (0, 0).  The ring table walks clockwise on screen and a north-up map keeps that sense, so every ring is written from its
+    first vertex against the walk: exterior rings counter-clockwise and holes clockwise, as RFC 7946 asks.  Properties:
+    "class" (the class value of the component), "pixels" (the component's pixel count: the sum of its rings' area2 over 2) and "area"
+    (pixels * sx * sy; null without a pixel scale).  No "crs" member is written: the coordinates are in the raster's own coordinate
+    reference system, not necessarily the WGS 84 of RFC 7946, and whoever reads the file must know it.  classes: the map the rings
+    were traced on, a tensor or an array."""
+    label, ring_id, start, area2, verts = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in rings)
+    flat = (classes.cpu().numpy() if torch.is_tensor(classes) else np.asarray(classes)).ravel()
+    sx, sy = (1.0, 1.0) if pixel_scale is None else (float(pixel_scale[0]), float(pixel_scale[1]))
+    ox, oy = (0.0, 0.0) if origin is None else (float(origin[0]), float(origin[1]))
+    xy = np.empty((verts.shape[0], 2), np.float64)
+    xy[:, 0] = ox + verts[:, 0].astype(np.float64) * sx
+    xy[:, 1] = oy - verts[:, 1].astype(np.float64) * sy
+    xy, first = xy.tolist(), start.tolist()                             # one conversion each: the loop below slices lists
+    order = np.argsort(label, kind="stable")                            # rings are in ascending ring id: the exterior (4 * label) leads
+    by_label, twice, owner = order.tolist(), area2[order].tolist(), label[order].tolist()
+    features, i, n = [], 0, len(by_label)
+    collecting = gc.isenabled()                                         # millions of small lists and no cycle among them: the cycle
+    gc.disable()                                                        # collector would walk them again and again, 3 x the time
+    try:
+        while i < n:
+            l, coords, total = owner[i], [], 0
+            while i < n and owner[i] == l:
+                ring = xy[first[by_label[i]]:first[by_label[i] + 1]]
+                coords.append(ring[:1] + ring[:0:-1] + ring[:1])            # from the first vertex, against the walk
+                total += twice[i]
+                i += 1
+            pixels = total // 2
+            features.append({"type": "Feature",
+                             "properties": {"class": int(flat[l]), "pixels": pixels, "area": None if pixel_scale is None else pixels * sx * sy},
+                             "geometry": {"type": "Polygon", "coordinates": coords}})
+    finally:
+        if collecting:
+            gc.enable()
+    return {"type": "FeatureCollection", "features": features}
 
 
 # ---------------------------------------------------------------------------------------------------- the scene loop

@@ -5,7 +5,8 @@
       --post VV.tif VH.tif --pre1 VV.tif VH.tif [--pre2 ...] [--dem dem.tif] \\
       --out flood.tif [--score softmax --score_out prob.tif] \\
       [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] \\
-      [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json]
+      [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
+      [--polygons flood.geojson --polygon_classes 1 2]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
 nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
@@ -19,7 +20,14 @@ live on one device: a scene that does not fit is outside this tool, as are --slo
 components of at least N pixels have; invalid pixels are never changed and never vote; --sieve_passes repeats the pass on its own
 output.  The scores of --score_out describe the blend, not the sieved map.  --report FILE.json writes what the map holds, counted on
 the class map as written: "pixel_counts" per class 0 .. 3, "pixel_area" (the product of the first post file's pixel scale, in map
-units squared; null without georeferencing), "class_area" per class, "mmu", "connectivity", "passes" and "components_removed"."""
+units squared; null without georeferencing), "class_area" per class, "mmu", "connectivity", "passes" and "components_removed".
+
+--polygons FILE.geojson writes the class map as written (after --mmu) as a vector layer, traced on the device
+(kurosiwo_amd.scene.polygonize, polygons_geojson): one Polygon feature per edge-connected component of the classes of
+--polygon_classes (default 1 2: the two water classes), whatever --connectivity the sieve ran with; the exterior ring first
+(counter-clockwise), then its holes; vertices are pixel corners in the georeferencing of the first post file (pixel coordinates with
+y negated without one), collinear vertices dropped; properties "class", "pixels" and "area".  No "crs" member is written: the
+coordinates are in the raster's own coordinate reference system."""
 import argparse
 import json
 import os
@@ -36,7 +44,7 @@ if ROOT not in sys.path:
 from kurosiwo_amd import geotiff                                            # noqa: E402
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
-from kurosiwo_amd.scene import cd_forward, predict_scene, seg_forward, sieve                      # noqa: E402
+from kurosiwo_amd.scene import cd_forward, polygonize, polygons_geojson, predict_scene, seg_forward, sieve      # noqa: E402
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -65,6 +73,8 @@ parser.add_argument("--mmu", type=int, default=None, help="minimum mapping unit 
 parser.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
 parser.add_argument("--sieve_passes", type=int, default=1)
 parser.add_argument("--report", default=None, help="FILE.json: per-class pixel counts and areas of the map as written")
+parser.add_argument("--polygons", default=None, help="FILE.geojson: the components of --polygon_classes of the map as written, as polygons")
+parser.add_argument("--polygon_classes", type=int, nargs="+", default=[1, 2])
 
 
 def read_date(paths, nodata):
@@ -114,6 +124,8 @@ def main(argv=None):
         raise SystemExit("predict.py: --score and --score_out come together")
     if args.sieve_passes < 1:
         raise SystemExit("predict.py: --sieve_passes >= 1")
+    if any(not 0 <= c <= 62 for c in args.polygon_classes):
+        raise SystemExit("predict.py: --polygon_classes takes class values 0 .. 62")
     method = args.method.lower()
     task = args.task or ("cd" if method in CD_METHODS else "segmentation")
     dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
@@ -183,6 +195,13 @@ def main(argv=None):
                        "mmu": args.mmu, "connectivity": args.connectivity, "passes": args.sieve_passes, "components_removed": removed}, f,
                       indent=1)
         print(f"wrote {args.report}")
+    if args.polygons is not None:
+        rings = polygonize(classes, select=args.polygon_classes)
+        collection = polygons_geojson(rings, written, pixel_scale=geo["pixel_scale"], origin=geo["origin"])
+        with open(args.polygons, "w") as f:
+            json.dump(collection, f)
+        print(f"wrote {args.polygons}: {len(collection['features'])} features, {rings.label.numel()} rings of classes "
+              f"{' '.join(str(c) for c in args.polygon_classes)}")
     if score is not None:
         geotiff.write(args.score_out, score.cpu().numpy(), nodata=float("nan"), **where)
         print(f"wrote {args.score_out}: {score.shape[0]} bands of {args.score}")

@@ -1,7 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
-                                [--mmu N [--connectivity 4] [--sieve_only]]
+                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -18,6 +18,13 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              ksmi_scene_label (3 launches), ksmi_scene_component_sizes (memset + 1), ksmi_scene_sieve_vote (2), ksmi_scene_sieve_apply
              (1), and their sum; where scipy is installed, scipy.ndimage.label per class on the host for the same map.  --sieve_only
              skips the model passes above.
+  polygons   with --polygons (the numbers behind profiles/polygon_probe.txt): kurosiwo_amd.scene.polygonize on a size x size class map of
+             the same three contents (the one class is class 1; classes 1 and 2 selected), as the event time of each stage: the
+             4-connectivity labels it starts from, ksmi_scene_edge_count, the four scans (pixels, ring heads, ring lengths, turn flags),
+             ksmi_scene_edge_emit, the two phases of ksmi_scene_ring_trace (ring minima, ranks), the assembly (ring_heads, ring_table,
+             ring_order, ring_verts), and their sum without the labels; then polygons_geojson on the host by the wall clock, where the
+             map has at most --geojson_max_rings rings (a Python list per ring: the checkerboard's ten million would take minutes).
+             --polygons_only skips the model passes above.
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -42,6 +49,9 @@ def main():
     ap.add_argument("--mmu", type=int, default=None)
     ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
     ap.add_argument("--sieve_only", action="store_true", default=False)
+    ap.add_argument("--polygons", action="store_true", default=False)
+    ap.add_argument("--polygons_only", action="store_true", default=False)
+    ap.add_argument("--geojson_max_rings", type=int, default=2_000_000)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -68,7 +78,11 @@ def main():
 
     if a.mmu is not None:
         sieve_probe(a, emit, ev, med)
-        if a.sieve_only:
+        if a.sieve_only and not a.polygons:
+            return finish()
+    if a.polygons:
+        polygon_probe(a, emit, ev, med)
+        if a.polygons_only or a.sieve_only:
             return finish()
     data = load_json5(os.path.join(HERE, "configs", "train", "data_config.json"))
     norm = (data["data_mean"], data["data_std"], [data["clamp_input"]] * 2)
@@ -234,6 +248,85 @@ def sieve_probe(a, emit, ev, med):
         emit(what="sieve", content=name, size=S, mmu=mmu, connectivity=conn, components=components, removed=first[2],
              label_ms=round(t[0], 3), sizes_ms=round(t[1], 3), vote_ms=round(t[2], 3), apply_ms=round(t[3], 3), total_ms=round(sum(t), 3),
              mpixels_per_s=round(S * S / sum(t) * 1e-3, 1), scipy_label_host_ms=host)
+
+
+def polygon_probe(a, emit, ev, med):
+    """polygonize on three maps of a.size x a.size, timed per stage; the sequence of kurosiwo_amd.scene.polygonize with an event
+    between its stages"""
+    import time
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib, scene
+    from kurosiwo_amd.runtime import stream_ptr
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    S, select, lib, st = a.size, (1, 2), _lib.load(), stream_ptr()
+    mask = sum(1 << c for c in select)
+    yy, xx = np.mgrid[0:S, 0:S]
+    maps = {"one_class": np.ones((S, S), np.uint8), "speckle": sieve_ref.speckle_scene(4480, S, S), "checkerboard": ((yy + xx) & 1).astype(np.uint8)}
+    del yy, xx
+    ptr = lambda t: t.data_ptr()
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device="cuda")
+    stages = ("label", "count", "scans", "emit", "trace_min", "trace_rank", "assembly")
+    for name, m in maps.items():
+        d = torch.from_numpy(m).cuda()
+
+        def one_pass():
+            t = dict.fromkeys(stages, 0.0)
+            marks = []
+
+            def stage(key, fn):
+                e0, e1 = ev(), ev()
+                e0.record()
+                out = fn()
+                e1.record()
+                marks.append((key, e0, e1))
+                return out
+            chk = _lib.check
+            lab = stage("label", lambda: scene.label_components(d, 4))
+            offs = i32(S * S)
+            stage("count", lambda: chk(lib.ksmi_scene_edge_count(ptr(d), ptr(lab), mask, S, S, ptr(offs), st), "scene_edge_count"))
+            E = int(stage("scans", lambda: scene._scan(offs, offs, "scan_i32")).item())
+            eid, succ, ring_min, rank, ridx, scratch = i32(E), i32(E), i32(E), i32(E), i32(E), i32(4 * E)
+            stage("emit", lambda: chk(lib.ksmi_scene_edge_emit(ptr(d), ptr(lab), mask, S, S, ptr(offs), E, ptr(eid), ptr(succ), st), "scene_edge_emit"))
+            for key, phase in (("trace_min", 1), ("trace_rank", 2)):
+                stage(key, lambda: chk(lib.ksmi_scene_ring_trace(ptr(succ), E, phase, ptr(ring_min), ptr(rank), ptr(scratch), 4 * E, st),
+                                       "scene_ring_trace"))
+            del scratch
+            stage("assembly", lambda: chk(lib.ksmi_scene_ring_heads(ptr(ring_min), E, ptr(ridx), st), "scene_ring_heads"))
+            R = int(stage("scans", lambda: scene._scan(ridx, ridx, "scan_i32")).item())
+            ring_id, label, roff = i32(R), i32(R), i32(R)
+            stage("assembly", lambda: chk(lib.ksmi_scene_ring_table(ptr(eid), ptr(succ), ptr(ring_min), ptr(rank), ptr(ridx), ptr(lab), S * S, E, R,
+                                                                    ptr(ring_id), ptr(label), ptr(roff), st), "scene_ring_table"))
+            stage("scans", lambda: scene._scan(roff, roff, "scan_i32"))
+            oeid, oring, voff = i32(E), i32(E), i32(E)
+            stage("assembly", lambda: chk(lib.ksmi_scene_ring_order(ptr(eid), ptr(succ), ptr(ring_min), ptr(rank), ptr(ridx), ptr(roff), E, R,
+                                                                    ptr(oeid), ptr(oring), ptr(voff), st), "scene_ring_order"))
+            V = int(stage("scans", lambda: scene._scan(voff, voff, "scan_i32")).item())
+            verts, start, area2 = i32(2 * V).view(V, 2), i32(R + 1), torch.empty(R, dtype=torch.int64, device="cuda")
+            stage("assembly", lambda: chk(lib.ksmi_scene_ring_verts(ptr(oeid), ptr(oring), ptr(voff), E, R, V, S, ptr(verts), ptr(start),
+                                                                    ptr(area2), st), "scene_ring_verts"))
+            torch.cuda.synchronize()
+            for key, e0, e1 in marks:
+                t[key] += e0.elapsed_time(e1)
+            return t, scene.Rings(label, ring_id, start, area2, verts), E
+        _, first, E = one_pass()                                               # warm-up
+        whole = scene.polygonize(d, select)
+        assert all(torch.equal(x, y) for x, y in zip(first, whole))            # the staged sequence is polygonize
+        runs = [one_pass() for _ in range(a.repeats)]
+        assert all(torch.equal(x, y) for x, y in zip(first, runs[-1][1]))      # equal bits
+        t = {k: med(r[0][k] for r in runs) for k in stages}
+        total = sum(v for k, v in t.items() if k != "label")
+        R, V = first.label.numel(), first.verts.shape[0]
+        host, features = None, None
+        if R <= a.geojson_max_rings:
+            t0 = time.perf_counter()
+            features = len(scene.polygons_geojson(first, d, pixel_scale=(10.0, 10.0), origin=(500000.0, 4100000.0))["features"])
+            host = round((time.perf_counter() - t0) * 1e3, 1)
+        emit(what="polygons", content=name, size=S, select=list(select), edges=E, rings=R, vertices=V, features=features,
+             rounds_per_phase=max(E - 1, 0).bit_length(), **{k + "_ms": round(v, 3) for k, v in t.items()},
+             total_without_label_ms=round(total, 3), mpixels_per_s=round(S * S / total * 1e-3, 1), geojson_host_ms=host)
+        del runs, first, whole
 
 
 if __name__ == "__main__":
