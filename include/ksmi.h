@@ -756,6 +756,27 @@ int ksmi_scene_accumulate(const float* logits, const int32_t* ys, int ny, const 
  * must be positive everywhere (a grid that covers the scene); 1 <= K <= 8. */
 int ksmi_scene_finalize(const float* acc, const float* wsum, const unsigned char* valid, int K, int64_t HW, int invalid_class,
                         unsigned char* out_class_u8, float* out_score, int score_mode, void* stream);
+/* Test-time views of the windows (csrc/scene.hip; kurosiwo_amd/scene.py: predict_scene(tta=...), predict.py --tta).  A view code v in
+ * 0 .. 7 names a symmetry of a tile T [h][w]: bit 2 transposes (applied first; needs h == w), bit 1 then flips y, bit 0 then flips x:
+ * U = v & 4 ? T^t : T; v & 2: U = U[::-1, :]; v & 1: U = U[:, ::-1].  The inverse undoes the flips, then the transpose.  A code
+ * outside 0 .. 7, or v & 4 with h != w, is KSMI_E_ARG and launches nothing.  tests/scene_tta_ref.py restates all three in numpy.
+ *   ksmi_scene_gather_view: replaces torch.flip / transpose of the gathered windows.  out[slot][c] = view `view` of what
+ *   ksmi_scene_gather writes there: the same arithmetic, nodata rule and +0.0f outside the scene; view 0 gives its bits.  Flips are
+ *   index arithmetic; a transposed view stages 64 x 64 tiles through LDS, so the raster is read along x and out written along x. */
+int ksmi_scene_gather_view(const float* raster, int C, int Hs, int Ws, const int32_t* ys, int ny, const int32_t* xs, int nx, int i0, int n, int h,
+                           int w, const float* mean, const float* stdv, const float* clamp, float nodata, int view, float* out, void* stream);
+/* ksmi_scene_unview: replaces the torch un-flip / transpose of the model's logits.  out[p] = the inverse view of in[p] for `planes`
+ * planes of [h][w] fp32, out of place (out == in is KSMI_E_ARG; the buffers must not overlap): a copy of bits, NaN payloads kept.
+ * planes = 0 is a no-op, planes < 0 KSMI_E_ARG. */
+int ksmi_scene_unview(const float* in, float* out, int64_t planes, int h, int w, int view, void* stream);
+/* ksmi_scene_accumulate_views: replaces V ksmi_scene_accumulate launches per batch, whose sums would run (batch, view, window) and so
+ * depend on the batch size.  logits [V][n][K][h][w] fp32 in window orientation (after ksmi_scene_unview).  Per scene pixel, over the
+ * covering windows of this launch in ascending i and for each the views in ascending v: acc_k = acc_k + (weight * logit_k), wsum =
+ * wsum + weight, rounded as in ksmi_scene_accumulate; weight is indexed at the window cell.  ksmi_scene_finalize then divides by the
+ * summed weights: the mean over windows and views, in logit space.  1 <= V <= 8, 1 <= K <= 8; V = 1 gives the bits of
+ * ksmi_scene_accumulate. */
+int ksmi_scene_accumulate_views(const float* logits, int V, const int32_t* ys, int ny, const int32_t* xs, int nx, int i0, int n, int K, int h, int w,
+                                const float* weight, float* acc, float* wsum, int Hs, int Ws, void* stream);
 /* Minimum mapping unit for the class map of a scene (csrc/sieve.hip; kurosiwo_amd/scene.py: label_components, component_sizes, sieve;
  * predict.py --mmu).  The reference has no counterpart: it stops at per-tile metrics and never maps a scene.  Integers throughout,
  * independent of launch geometry and arrival order; tests/sieve_ref.py restates every entry as a flood fill in numpy.  A scene has at

@@ -192,6 +192,9 @@ SIGNATURES = {
     "ksmi_scene_gather": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
     "ksmi_scene_accumulate": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "ksmi_scene_finalize": (_i, [_vp, _vp, _vp, _i, _i64, _i, _vp, _vp, _i, _vp]),
+    "ksmi_scene_gather_view": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp]),
+    "ksmi_scene_unview": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
+    "ksmi_scene_accumulate_views": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "ksmi_scene_label": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "ksmi_scene_component_sizes": (_i, [_vp, _i64, _vp, _vp]),
     "ksmi_scene_sieve_vote": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -5,7 +5,9 @@ ksmi_scene_gather per input raster cuts and normalises the batch's windows (the 
 under torch.no_grad(), and one ksmi_scene_accumulate adds weight * logits onto the scene in gather form (one thread per scene pixel,
 the covering windows in ascending order, no atomics: the blend is bitwise reproducible and equals the numpy slice loop of
 tests/scene_ref.py).  ksmi_scene_valid marks the pixels where some input is NaN or the nodata sentinel, ksmi_scene_finalize divides
-by the summed weights and takes the first maximum.  `sieve` (csrc/sieve.hip) then applies a minimum mapping unit to the class map:
+by the summed weights and takes the first maximum.  With test-time views (`tta`: VIEW_SETS) every window goes through the model once
+per flipped / transposed view: ksmi_scene_gather_view cuts the windows already turned, ksmi_scene_unview turns the logits back, and
+one ksmi_scene_accumulate_views per batch sums the views inside the pixel's window walk (tests/scene_tta_ref.py).  `sieve` (csrc/sieve.hip) then applies a minimum mapping unit to the class map:
 connected components by a tile-local union-find and border merges, their sizes, and a vote of the large neighbours for every small
 component; integers throughout, equal to the flood fill of tests/sieve_ref.py.  `polygonize` (csrc/polygon.hip) turns the class map
 into boundary rings: the boundary edges of the 4-connected components, each with its successor, the rings by pointer doubling, and the
@@ -26,6 +28,23 @@ SCAN_TILE = 2048                  # SCAN_TILE of csrc/polygon.hip: the elements 
 MAX_POLYGON_PIXELS = 2 ** 29 - 1  # edge ids 4 * p + s and the edge count fit int32
 Rings = namedtuple("Rings", "label ring_id start area2 verts")
 SCORES = {None: None, "logits": 0, "softmax": 1}
+# test-time view sets, in ascending code; a code's bit 2 transposes the window (first), bit 1 then flips y, bit 0 then flips x
+VIEW_SETS = {"hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def _views(tta):
+    """predict_scene's tta -> None (no views: one pass) or the view codes in ascending order"""
+    if tta is None or tta == "none":
+        return None
+    if isinstance(tta, str):
+        if tta not in VIEW_SETS:
+            raise ValueError(f'predict_scene: tta is None, "none", one of {sorted(VIEW_SETS)} or a tuple of view codes 0 .. 7, got {tta!r}')
+        return VIEW_SETS[tta]
+    codes = list(tta) if isinstance(tta, (tuple, list)) else None
+    if not codes or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 7 for v in codes) \
+            or len(set(int(v) for v in codes)) != len(codes):
+        raise ValueError(f"predict_scene: tta as a tuple holds distinct view codes 0 .. 7, at least one, got {tta!r}")
+    return tuple(sorted(int(v) for v in codes))
 
 
 def _axis(L, win, s):
@@ -92,23 +111,60 @@ def _check_grid(ys, xs, name):
             raise ValueError(f"{name}: ys and xs are contiguous int32 device vectors")
 
 
-def scene_gather(raster, ys, xs, i0, n, h, w, norm=None, nodata=None, out=None):
-    """ksmi_scene_gather: windows i0 .. i0 + n - 1 of raster [C, Hs, Ws] as [n, C, h, w]; norm = (mean, std, clamp) float32 device
-    vectors of C entries, or None for raw values (nodata -> NaN)"""
-    _check_raster(raster, "scene_gather")
-    _check_grid(ys, xs, "scene_gather")
+def _gather(name, raster, ys, xs, i0, n, h, w, norm, nodata, out, view=None):
+    _check_raster(raster, name)
+    _check_grid(ys, xs, name)
     C, Hs, Ws = raster.shape
     if out is None:
         out = torch.empty((max(n, 0), C, h, w), dtype=torch.float32, device=raster.device)
     elif out.dtype != torch.float32 or out.shape != (n, C, h, w) or out.device != raster.device or not out.is_contiguous():
-        raise ValueError("scene_gather: out is a contiguous float32 tensor [n, C, h, w] on the raster's device")
+        raise ValueError(f"{name}: out is a contiguous float32 tensor [n, C, h, w] on the raster's device")
     if norm is not None:
         for t in norm:
             if t.dtype != torch.float32 or t.numel() != C or t.device != raster.device or not t.is_contiguous():
-                raise ValueError(f"scene_gather: mean, std and clamp are float32 device vectors of {C} entries")
+                raise ValueError(f"{name}: mean, std and clamp are float32 device vectors of {C} entries")
     m, s, c = (None, None, None) if norm is None else (t.data_ptr() for t in norm)
-    _lib.check(_lib.load().ksmi_scene_gather(raster.data_ptr(), C, Hs, Ws, ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, h, w,
-                                             m, s, c, _nodata(nodata), out.data_ptr(), stream_ptr()), "scene_gather")
+    head = (raster.data_ptr(), C, Hs, Ws, ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, h, w, m, s, c, _nodata(nodata))
+    if view is None:
+        _lib.check(_lib.load().ksmi_scene_gather(*head, out.data_ptr(), stream_ptr()), name)
+    else:
+        _lib.check(_lib.load().ksmi_scene_gather_view(*head, int(view), out.data_ptr(), stream_ptr()), name)
+    return out
+
+
+def scene_gather(raster, ys, xs, i0, n, h, w, norm=None, nodata=None, out=None):
+    """ksmi_scene_gather: windows i0 .. i0 + n - 1 of raster [C, Hs, Ws] as [n, C, h, w]; norm = (mean, std, clamp) float32 device
+    vectors of C entries, or None for raw values (nodata -> NaN)"""
+    return _gather("scene_gather", raster, ys, xs, i0, n, h, w, norm, nodata, out)
+
+
+def _check_view(view, h, w, name):
+    if isinstance(view, bool) or not isinstance(view, (int, np.integer)) or not 0 <= int(view) <= 7:
+        raise ValueError(f"{name}: view is a code 0 .. 7 (1: flip x, 2: flip y, 4: transpose), got {view!r}")
+    if int(view) & 4 and h != w:
+        raise ValueError(f"{name}: a transposed view needs h == w, got {h} x {w}")
+
+
+def scene_gather_view(raster, ys, xs, i0, n, h, w, view, norm=None, nodata=None, out=None):
+    """ksmi_scene_gather_view: scene_gather with every [h, w] tile in view `view` (0 .. 7: bit 2 transposes first, bit 1 then flips y,
+    bit 0 then flips x); view 0 gives the bits of scene_gather"""
+    _check_view(view, h, w, "scene_gather_view")
+    return _gather("scene_gather_view", raster, ys, xs, i0, n, h, w, norm, nodata, out, view)
+
+
+def scene_unview(x, view, out=None):
+    """ksmi_scene_unview: the inverse of view `view` on every [h, w] plane of the contiguous float32 device tensor x [..., h, w], out of
+    place; a copy of bits.  out: a contiguous tensor of x's shape that shares no memory with it"""
+    require_gpu(x)
+    if x.dtype != torch.float32 or x.dim() < 2 or not x.is_contiguous() or x.shape[-1] < 1 or x.shape[-2] < 1:
+        raise ValueError("scene_unview: x is a contiguous float32 tensor [..., h, w]")
+    h, w = x.shape[-2:]
+    _check_view(view, h, w, "scene_unview")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device or not out.is_contiguous():
+        raise ValueError("scene_unview: out is a contiguous float32 tensor of x's shape on its device")
+    _lib.check(_lib.load().ksmi_scene_unview(x.data_ptr(), out.data_ptr(), x.numel() // (h * w), h, w, int(view), stream_ptr()), "scene_unview")
     return out
 
 
@@ -125,6 +181,22 @@ def scene_accumulate(logits, ys, xs, i0, weight, acc, wsum):
     _lib.check(_lib.load().ksmi_scene_accumulate(logits.data_ptr(), ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, K, h, w,
                                                  weight.data_ptr(), acc.data_ptr(), wsum.data_ptr(), acc.shape[1], acc.shape[2], stream_ptr()),
                "scene_accumulate")
+
+
+def scene_accumulate_views(logits, ys, xs, i0, weight, acc, wsum):
+    """ksmi_scene_accumulate_views: scene_accumulate over logits [V, n, K, h, w], the V views of windows i0 .. in window orientation
+    (after scene_unview): per scene pixel the covering windows in ascending order and for each the views in ascending order"""
+    require_gpu(logits)
+    _check_grid(ys, xs, "scene_accumulate_views")
+    if logits.dtype != torch.float32 or logits.dim() != 5 or not logits.is_contiguous():
+        raise ValueError("scene_accumulate_views: logits is a contiguous float32 tensor [V, n, K, h, w]")
+    V, n, K, h, w = logits.shape
+    if acc.dim() != 3 or acc.shape[0] != K or wsum.shape != acc.shape[1:] or weight.shape != (h, w) or any(
+            t.dtype != torch.float32 or not t.is_contiguous() or t.device != logits.device for t in (weight, acc, wsum)):
+        raise ValueError("scene_accumulate_views: float32 contiguous weight [h, w], acc [K, Hs, Ws] and wsum [Hs, Ws] on the logits' device")
+    _lib.check(_lib.load().ksmi_scene_accumulate_views(logits.data_ptr(), V, ys.data_ptr(), ys.numel(), xs.data_ptr(), xs.numel(), i0, n, K, h, w,
+                                                       weight.data_ptr(), acc.data_ptr(), wsum.data_ptr(), acc.shape[1], acc.shape[2],
+                                                       stream_ptr()), "scene_accumulate_views")
 
 
 def scene_finalize(acc, wsum, valid=None, score=None, invalid_class=3):
@@ -409,7 +481,7 @@ def polygons_geojson(rings, classes, pixel_scale=None, origin=None):
 
 # ---------------------------------------------------------------------------------------------------- the scene loop
 def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, weight="hann", nodata=None, score=None, raw=False,
-                  invalid_class=3, mmu=None, connectivity=4):
+                  invalid_class=3, mmu=None, connectivity=4, tta=None):
     """A class map of a whole scene.
 
     rasters: device float32 [C_i, Hs, Ws], one per model input (e.g. pre, post, DEM), all of one size.
@@ -422,9 +494,16 @@ def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, wei
     score:   None, "logits" (the blended mean logits) or "softmax".
     mmu:     None, or the minimum mapping unit in pixels: the class map goes through one pass of `sieve` at `connectivity` (4 or 8)
              over the model's K classes.  The scores are returned unchanged: they describe the blend, not the sieved map.
+    tta:     None or "none": one pass.  A name of VIEW_SETS ("hflip": identity and x flip; "flips": the four flips; "d4": those and
+             their transposes) or a tuple of distinct view codes 0 .. 7 (taken in ascending order): every window goes through the model
+             once per view (scene_gather_view), the logits are turned back (scene_unview) and all views enter the blend with the
+             window's weight (scene_accumulate_views), so the map is the weighted mean over windows and views, in logit space, and its
+             bits still do not depend on `batch`.  V views cost V times the model time and a [V, batch, K, h, w] float32 buffer.
+             (0,) takes this path and gives the bits of None.
     Returns (classes uint8 [Hs, Ws] with `invalid_class` where some input is missing, scores float32 [K, Hs, Ws] or None)."""
     if score not in SCORES:
         raise ValueError(f'predict_scene: score is None, "logits" or "softmax", got {score!r}')
+    views = _views(tta)
     if mmu is not None and connectivity not in (4, 8):
         raise ValueError(f"predict_scene: connectivity is 4 or 8, got {connectivity!r}")
     if not rasters or len(norms) != len(rasters):
@@ -452,18 +531,39 @@ def predict_scene(forward, rasters, norms, window=224, stride=112, batch=32, wei
         dev_norms.append(None if raw else tuple(v.to(dev) for v in vecs))
     ys, xs, wt = torch.from_numpy(ys_h).to(dev), torch.from_numpy(xs_h).to(dev), torch.from_numpy(wt_h).to(dev)
     total = len(ys_h) * len(xs_h)
-    acc = wsum = None
+    acc = wsum = slabs = None
+
+    def window_logits(i0, n, view):
+        if view is None:
+            tiles = [scene_gather(r, ys, xs, i0, n, h, w, nm, nd) for r, nm, nd in zip(rasters, dev_norms, nodatas)]
+        else:
+            tiles = [scene_gather_view(r, ys, xs, i0, n, h, w, view, nm, nd) for r, nm, nd in zip(rasters, dev_norms, nodatas)]
+        logits = forward(tiles).float().contiguous()
+        if logits.dim() != 4 or logits.shape[0] != n or logits.shape[2:] != (h, w) or not 1 <= logits.shape[1] <= MAX_CLASSES:
+            raise ValueError(f"predict_scene: forward returned {tuple(logits.shape)}, expected [{n}, K <= {MAX_CLASSES}, {h}, {w}]")
+        return logits
+
     with torch.no_grad():
         for i0 in range(0, total, int(batch)):
             n = min(int(batch), total - i0)                               # the ragged last batch passes its own n
-            tiles = [scene_gather(r, ys, xs, i0, n, h, w, nm, nd) for r, nm, nd in zip(rasters, dev_norms, nodatas)]
-            logits = forward(tiles).float().contiguous()
-            if logits.dim() != 4 or logits.shape[0] != n or logits.shape[2:] != (h, w) or not 1 <= logits.shape[1] <= MAX_CLASSES:
-                raise ValueError(f"predict_scene: forward returned {tuple(logits.shape)}, expected [{n}, K <= {MAX_CLASSES}, {h}, {w}]")
+            logits = window_logits(i0, n, None if views is None else views[0])
             if acc is None:
-                acc = torch.zeros((logits.shape[1], Hs, Ws), dtype=torch.float32, device=dev)
+                K = logits.shape[1]
+                acc = torch.zeros((K, Hs, Ws), dtype=torch.float32, device=dev)
                 wsum = torch.zeros((Hs, Ws), dtype=torch.float32, device=dev)
-            scene_accumulate(logits, ys, xs, i0, wt, acc, wsum)
+                if views is not None:                                     # one buffer per scene; a ragged batch uses its head
+                    slabs = torch.empty(len(views) * min(int(batch), total) * K * h * w, dtype=torch.float32, device=dev)
+            if views is None:
+                scene_accumulate(logits, ys, xs, i0, wt, acc, wsum)
+                continue
+            stack = slabs[:len(views) * n * K * h * w].view(len(views), n, K, h, w)
+            for j, v in enumerate(views):
+                if j:
+                    logits = window_logits(i0, n, v)
+                if logits.shape[1] != K:
+                    raise ValueError(f"predict_scene: forward returned {logits.shape[1]} classes after {K}")
+                scene_unview(logits, v, out=stack[j])
+            scene_accumulate_views(stack, ys, xs, i0, wt, acc, wsum)
         valid = None
         for r, nd in zip(rasters, nodatas):
             valid = scene_valid(r, nd, valid)

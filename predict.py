@@ -4,7 +4,7 @@
   python predict.py --task cd --method snunet --checkpoint best.pt \\
       --post VV.tif VH.tif --pre1 VV.tif VH.tif [--pre2 ...] [--dem dem.tif] \\
       --out flood.tif [--score softmax --score_out prob.tif] \\
-      [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] \\
+      [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] [--tta hflip] \\
       [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
       [--polygons flood.geojson --polygon_classes 1 2]
 
@@ -13,7 +13,15 @@ nodata tag is the sentinel of its date (--nodata overrides it); a pixel where an
 ("Invalid pixels").  The DEM's gaps are filled on the host as the loaders fill them, and the DEM is standardised with the loaders'
 constants.  The class raster is a Deflate-compressed uint8 GeoTIFF in tiles of 256 with the first post file's georeferencing and
 nodata = 3; the scores, where asked for, a float32 multi-band file written the same way.  The scene, the accumulators and the outputs
-live on one device: a scene that does not fit is outside this tool, as are --slope, SLC products and test-time flips.
+live on one device: a scene that does not fit is outside this tool, as are --slope and SLC products.
+
+--tta SET runs every window through the model once per view of SET and blends all views on the device, each with the window's weight
+(kurosiwo_amd.scene.predict_scene(tta=SET): the mean over windows and views is taken in logit space, as the windows' already is;
+probabilities are not averaged).  none (the default): one pass.  hflip: the window and its left-right mirror image, the orientation
+the training augmentation (HorizontalFlip, configs/augmentations/augmentation.json) has shown the model.  flips: the four
+combinations of the left-right and the up-down flip.  d4: those four and their transposes, all eight symmetries of the square.
+flips and d4 show the model orientations it was not trained on: whether they help depends on the model.  V views cost V times the
+model time and V * batch_size * classes * window^2 * 4 bytes more device memory; the map does not depend on --batch_size.
 
 --mmu N applies a minimum mapping unit on the device before the map is written (kurosiwo_amd.scene.sieve): every connected component
 (--connectivity 4: joined by edges, 8: by edges and corners) of fewer than N pixels takes the class most of its edge neighbours in
@@ -67,6 +75,8 @@ parser.add_argument("--stride", type=int, default=112)
 parser.add_argument("--weight", choices=("hann", "uniform"), default="hann")
 parser.add_argument("--batch_size", type=int, default=32)
 parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
+parser.add_argument("--tta", choices=("none", "hflip", "flips", "d4"), default="none",
+                    help="test-time views blended on the device: the window and its mirror image / the four flips / all eight symmetries")
 parser.add_argument("--raw", action="store_true", default=False,
                     help="hand raw windows to a model that normalises inside its first convolution (snunet)")
 parser.add_argument("--mmu", type=int, default=None, help="minimum mapping unit in pixels: smaller components take their neighbours' class")
@@ -175,7 +185,7 @@ def main(argv=None):
         forward = seg_forward(model, inputs, dem=args.dem is not None)
     classes, score = predict_scene(forward, [torch.from_numpy(np.ascontiguousarray(r)).to(dev) for r in rasters], norms, window=args.window,
                                    stride=args.stride, batch=args.batch_size, weight=args.weight, nodata=nodatas, score=args.score,
-                                   raw=args.raw)
+                                   raw=args.raw, tta=args.tta)
     removed = 0
     if args.mmu is not None:                            # class 3 is the invalid class of the map: a vote table of at least 4 rows
         classes, gone = sieve(classes, args.mmu, args.connectivity, invalid_class=3, num_classes=max(4, int(configs["num_classes"])),

@@ -1,7 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
-                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]]
+                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -25,6 +25,13 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              ring_order, ring_verts), and their sum without the labels; then polygons_geojson on the host by the wall clock, where the
              map has at most --geojson_max_rings rings (a Python list per ring: the checkerboard's ten million would take minutes).
              --polygons_only skips the model passes above.
+  tta        with --tta SET [SET ...] of none, hflip, flips, d4 (the numbers behind profiles/tta_probe.txt), instead of the passes above:
+             per set the pass (predict_scene(tta=SET) end to end) and its split with an event after each stage of each view of each
+             batch: gather (ksmi_scene_gather_view, one launch per raster), forward (the model and the fp32 copy of its logits),
+             unview (ksmi_scene_unview) and accumulate (ksmi_scene_accumulate_views, one launch per batch); then the launches alone,
+             back to back between two events, at one batch and at all windows of the grid: gather_view and unview per view code (0 .. 3
+             index arithmetic, 4 .. 7 through the LDS tile transposer), and ksmi_scene_accumulate_views over 8 views against 8
+             ksmi_scene_accumulate launches on the same logits.
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -52,6 +59,7 @@ def main():
     ap.add_argument("--polygons", action="store_true", default=False)
     ap.add_argument("--polygons_only", action="store_true", default=False)
     ap.add_argument("--geojson_max_rings", type=int, default=2_000_000)
+    ap.add_argument("--tta", nargs="+", choices=("none", "hflip", "flips", "d4"), default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -102,6 +110,9 @@ def main():
     ys, xs = torch.from_numpy(ys_h).to(dev), torch.from_numpy(xs_h).to(dev)
     wt = torch.from_numpy(blend_weights(h, h, "hann")).to(dev)
     dev_norm = tuple(torch.tensor(v, dtype=torch.float32, device=dev) for v in norm)
+    if a.tta:
+        tta_probe(a, emit, ev, med, forward, rasters, norm, dev_norm, ys, xs, wt, starts, total, K)
+        return finish()
 
     def whole():
         e0, e1 = ev(), ev()
@@ -191,6 +202,122 @@ def main():
          same_bits=same, accumulate_bytes=nbytes, accumulate_tb_per_s=round(nbytes / med(tk) * 1e-9, 3), measured_hbm_tb_per_s=MEASURED_HBM_TBS,
          launches=len(starts))
     finish()
+
+
+def tta_probe(a, emit, ev, med, forward, rasters, norm, dev_norm, ys, xs, wt, starts, total, K):
+    """predict_scene(tta=SET) per set of a.tta: the pass, its split by stage, then the view launches alone"""
+    import torch
+    from kurosiwo_amd.scene import (VIEW_SETS, predict_scene, scene_accumulate, scene_accumulate_views, scene_finalize, scene_gather,
+                                    scene_gather_view, scene_unview, scene_valid)
+    S, h, dev = a.size, a.window, rasters[0].device
+    for name in a.tta:
+        views = None if name == "none" else VIEW_SETS[name]
+        V = 1 if views is None else len(views)
+
+        def whole():
+            e0, e1 = ev(), ev()
+            e0.record()
+            out = predict_scene(forward, rasters, [norm, norm], window=h, stride=a.stride, batch=a.batch, weight="hann", tta=name)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1), out[0]
+        _, first = whole()                                                     # warm-up
+        runs = [whole() for _ in range(a.repeats)]
+        assert all(torch.equal(first, c) for _, c in runs)                     # the map is the same in every pass, bit for bit
+        t = med([ms for ms, _ in runs])
+        emit(what="tta_pass", tta=name, views=V, size=S, window=h, stride=a.stride, batch=a.batch, precision=a.precision, windows=total,
+             batches=len(starts), ms_median=round(t, 2), ms_all=[round(ms, 2) for ms, _ in runs], windows_per_s=round(total / t * 1e3, 1),
+             classes=torch.bincount(first.flatten().long(), minlength=4).tolist())
+
+        def split():
+            stages, blends = [], []
+            acc, wsum = torch.zeros((K, S, S), device=dev), torch.zeros((S, S), device=dev)
+            slabs = None if views is None else torch.empty(V * a.batch * K * h * h, device=dev)
+            with torch.no_grad():
+                for i0 in starts:
+                    n = min(a.batch, total - i0)
+                    stack = None if views is None else slabs[:V * n * K * h * h].view(V, n, K, h, h)
+                    for j, v in enumerate(views or (None,)):
+                        e = [ev() for _ in range(4)]
+                        e[0].record()
+                        if v is None:
+                            tiles = [scene_gather(r, ys, xs, i0, n, h, h, dev_norm, None) for r in rasters]
+                        else:
+                            tiles = [scene_gather_view(r, ys, xs, i0, n, h, h, v, dev_norm, None) for r in rasters]
+                        e[1].record()
+                        logits = forward(tiles).float().contiguous()
+                        e[2].record()
+                        if v is not None:
+                            scene_unview(logits, v, out=stack[j])
+                        e[3].record()
+                        stages.append(e)
+                    b = (ev(), ev())
+                    b[0].record()
+                    if views is None:
+                        scene_accumulate(logits, ys, xs, i0, wt, acc, wsum)
+                    else:
+                        scene_accumulate_views(stack, ys, xs, i0, wt, acc, wsum)
+                    b[1].record()
+                    blends.append(b)
+                f0, f1 = ev(), ev()
+                f0.record()
+                valid = None
+                for r in rasters:
+                    valid = scene_valid(r, None, valid)
+                cls, _ = scene_finalize(acc, wsum, valid, None, 3)
+                f1.record()
+            torch.cuda.synchronize()
+            assert torch.equal(cls, first)
+            return [sum(e[j].elapsed_time(e[j + 1]) for e in stages) for j in range(3)] + [sum(b0.elapsed_time(b1) for b0, b1 in blends),
+                                                                                           f0.elapsed_time(f1)]
+        parts = [split() for _ in range(a.repeats)]
+        gat, fwd, unv, accu, fin = (med(p[j] for p in parts) for j in range(5))
+        glue = gat + unv + accu + fin
+        emit(what="tta_split", tta=name, views=V, gather_ms=round(gat, 3), forward_ms=round(fwd, 2), unview_ms=round(unv, 3),
+             accumulate_ms=round(accu, 3), valid_finalize_ms=round(fin, 3), glue_ms=round(glue, 3), model_share=round(fwd / (fwd + glue), 4),
+             glue_share=round(glue / (fwd + glue), 4))
+
+    def per_launch_us(fn, reps):
+        """median over a.repeats of: `reps` launches back to back between two events, per launch"""
+        fn()
+        out = []
+        for _ in range(a.repeats):
+            e0, e1 = ev(), ev()
+            e0.record()
+            for _ in range(reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) * 1e3 / reps)
+        return round(med(out), 2)
+
+    i0 = starts[len(starts) // 2]
+    for label, j0, n, reps in (("batch", i0, min(a.batch, total - i0), 100), ("grid", 0, total, 5)):
+        out = torch.empty((n, rasters[0].shape[0], h, h), device=dev)
+        gather = {"plain": per_launch_us(lambda: scene_gather(rasters[0], ys, xs, j0, n, h, h, dev_norm, None, out=out), reps)}
+        for v in range(8):
+            gather[str(v)] = per_launch_us(lambda: scene_gather_view(rasters[0], ys, xs, j0, n, h, h, v, dev_norm, None, out=out), reps)
+        del out
+        x, y = torch.randn((n, K, h, h), device=dev), torch.empty((n, K, h, h), device=dev)
+        unview = {str(v): per_launch_us(lambda: scene_unview(x, v, out=y), reps) for v in range(8)}
+        copy = per_launch_us(lambda: y.copy_(x), reps)
+        emit(what="tta_launches", shape=label, windows=n, gather_bytes=2 * n * rasters[0].shape[0] * h * h * 4, unview_bytes=2 * n * K * h * h * 4,
+             gather_us=gather, unview_us=unview, torch_copy_us=copy,
+             gather_transposed_over_flipped=round(med(gather[str(v)] for v in (4, 5, 6, 7)) / med(gather[str(v)] for v in (0, 1, 2, 3)), 2),
+             unview_transposed_over_flipped=round(med(unview[str(v)] for v in (4, 5, 6, 7)) / med(unview[str(v)] for v in (0, 1, 2, 3)), 2))
+        del x, y
+    n = min(a.batch, total - i0)
+    lg = torch.rand((8, n, K, h, h), device=dev) * 16 - 8
+    acc, wsum = torch.zeros((K, S, S), device=dev), torch.zeros((S, S), device=dev)
+
+    def eight():
+        for v in range(8):
+            scene_accumulate(lg[v], ys, xs, i0, wt, acc, wsum)
+    one_us = per_launch_us(lambda: scene_accumulate_views(lg, ys, xs, i0, wt, acc, wsum), 50)
+    eight_us = per_launch_us(eight, 50)
+    single_us = per_launch_us(lambda: scene_accumulate(lg[0], ys, xs, i0, wt, acc, wsum), 50)
+    emit(what="tta_accumulate", windows=n, views=8, accumulate_views_us=one_us, eight_accumulate_launches_us=eight_us,
+         one_accumulate_launch_us=single_us, eight_over_one=round(eight_us / one_us, 2))
 
 
 def sieve_probe(a, emit, ev, med):
