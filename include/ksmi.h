@@ -387,7 +387,7 @@ int ksmi_ecam_final_backward_reduce(const void* const x[4], const float* dlogits
                                     const float* wf, float* dca, float* dca1, float* dwf, float* dbias,
                                     float* workspace, int B, int HW, int C, int ncls, int dtype, void* stream);
 size_t ksmi_ecam_bwd_workspace(int B, int HW, int C, int ncls);
-/* MLP backward: dca,dca1 -> davg[B][5C], dmax[B][5C], and fc weight grads (+=) */
+/* MLP backward: dca,dca1 -> davg[B][5C], dmax[B][5C], and fc weight grads (=: overwritten) */
 int ksmi_ecam_mlp_backward(const float* avg, const float* mx, const float* hidden, const float* ca, const float* ca1,
                            const float* dca, const float* dca1, const float* ca_fc1, const float* ca_fc2,
                            const float* ca1_fc1, const float* ca1_fc2, float* davg, float* dmax,

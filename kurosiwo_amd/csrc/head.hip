@@ -131,7 +131,9 @@ __global__ void ecam_pool_final_kernel(const float* psum, const float* pmax, con
     a += (double)psum[o];
     if (pmax[o] > m || (pmax[o] == m && pidx[o] < ix)) { m = pmax[o]; ix = pidx[o]; }
   }
-  avg[i] = (float)(a / (double)HW); mx[i] = m; argmax[i] = ix;
+  // a channel in which nothing compared greater (all NaN, all -inf) keeps the start index: store pixel 0 instead, a pixel the max
+  // scatter of the backward may write to (avg is NaN / -inf there already, so the loss still shows it)
+  avg[i] = (float)(a / (double)HW); mx[i] = m; argmax[i] = ix == 0x7fffffff ? 0 : ix;
 }
 
 // tiny MLPs: one block per image.  hidden layout per image: [avg|max][h_ca (4C/16) + h_ca1 (C/4)]
