@@ -862,6 +862,38 @@ int ksmi_scene_ring_order(const int32_t* eid_i32, const int32_t* succ_i32, const
  * workgroup before the global integer add. */
 int ksmi_scene_ring_verts(const int32_t* ordered_eid_i32, const int32_t* ordered_ring_i32, const int32_t* vertex_offset_i32, int64_t E,
                           int64_t R, int64_t V, int Ws, int32_t* verts_i32, int32_t* start_i32, int64_t* area2_i64, void* stream);
+/* Flood depth for the class map of a scene (csrc/depth.hip; kurosiwo_amd/scene.py: nearest_feature, flood_depth; predict.py
+ * --depth_out).  The reference has no counterpart: it never maps a scene and never reads an elevation as one.  The transform is
+ * integers throughout (no float arithmetic, no atomics, nothing read on the host), independent of launch geometry;
+ * tests/depth_ref.py restates every entry in numpy.  Pixels are p = y * Ws + x.  A scene to transform has 1 <= Hs, Ws <= 32767, so
+ * that every squared distance (at most 2 * 32766^2 = 2147221512) stays below the sentinel 2^31 - 1 and Hs * Ws below 2^31; another
+ * size or a null pointer are KSMI_E_ARG and launch nothing.  Scratch is the caller's: 4 B of near_y per pixel.
+ *   ksmi_scene_edt_cols: the reference has no counterpart.  A non-zero mask_u8[p] marks a feature.  near_y_i32[y][x] = the row of the
+ *   nearest feature in column x, the smaller row when the one above and the one below are equally far, -1 when the column has none. */
+int ksmi_scene_edt_cols(const unsigned char* mask_u8, int Hs, int Ws, int32_t* near_y_i32, void* stream);
+/* ksmi_scene_edt_rows: the reference has no counterpart.  For pixel (y, x) the lexicographic minimum of the pair ((x - i)^2 +
+ * (y - near_y_i32[y][i])^2, near_y_i32[y][i] * Ws + i) over the columns i with a feature: dist2_i32[p] = the smallest squared
+ * Euclidean distance from p to a feature, nearest_i32[p] = the smallest linear index among the features at that distance.  With no
+ * feature in the scene dist2 = 2^31 - 1 and nearest = -1.  where_u8 may be NULL; where it is given and zero at p the pixel is skipped
+ * and gets the same two values.  A near_y value outside -1 .. Hs - 1 counts as -1. */
+int ksmi_scene_edt_rows(const int32_t* near_y_i32, const unsigned char* where_u8, int Hs, int Ws, int32_t* dist2_i32, int32_t* nearest_i32,
+                        void* stream);
+/* ksmi_scene_select: the reference has no counterpart.  out_u8[p] = 1 where the class of p is in the set, else 0.  Bit c of
+ * select_mask selects class c, 0 <= c <= 62, as in the polygon entries (a negative mask is KSMI_E_ARG).  HW = 0 is a no-op. */
+int ksmi_scene_select(const unsigned char* classes_u8, int64_t select_mask, int64_t HW, unsigned char* out_u8, void* stream);
+/* ksmi_scene_shore: the reference has no counterpart.  water(p): the class of p is in water_mask (a bit mask over class values 0 ..
+ * 62); valid(p): the class of p is not invalid_class.  shore_u8[p] = 1 where water(p), dem_f32[p] is finite and some 4-edge neighbour
+ * n inside the scene has valid(n) and not water(n); else 0.  A scene border or an invalid neighbour makes no shore: the water's real
+ * edge is not seen there (the FwDET v2 rule for coastlines and image edges). */
+int ksmi_scene_shore(const unsigned char* classes_u8, const float* dem_f32, int64_t water_mask, int invalid_class, int Hs, int Ws,
+                     unsigned char* shore_u8, void* stream);
+/* ksmi_scene_depth: the reference has no counterpart.  nearest_i32 = ksmi_scene_edt_rows of the shore with the water pixels as
+ * where_u8.  depth_f32[p], by the first rule that matches: NaN where p is not valid; +0.0f where p is valid and not water; NaN where
+ * p is water and nearest_i32[p] < 0 or dem_f32[p] is not finite; else d = dem_f32[nearest_i32[p]] - dem_f32[p] in one fp32
+ * subtraction and depth = d > 0 ? d : +0.0f, never -0.0f.  wse_f32 (may be NULL): dem_f32[nearest_i32[p]] where p is water and
+ * nearest_i32[p] >= 0, NaN elsewhere.  NaN is 0x7fc00000.  An index not below HW counts as negative.  HW = 0 is a no-op. */
+int ksmi_scene_depth(const unsigned char* classes_u8, const float* dem_f32, const int32_t* nearest_i32, int64_t water_mask, int invalid_class,
+                     int64_t HW, float* depth_f32, float* wse_f32, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

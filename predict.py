@@ -6,7 +6,8 @@
       --out flood.tif [--score softmax --score_out prob.tif] \\
       [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] [--tta hflip] \\
       [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
-      [--polygons flood.geojson --polygon_classes 1 2]
+      [--polygons flood.geojson --polygon_classes 1 2] \\
+      [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2]]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
 nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
@@ -35,7 +36,19 @@ units squared; null without georeferencing), "class_area" per class, "mmu", "con
 --polygon_classes (default 1 2: the two water classes), whatever --connectivity the sieve ran with; the exterior ring first
 (counter-clockwise), then its holes; vertices are pixel corners in the georeferencing of the first post file (pixel coordinates with
 y negated without one), collinear vertices dropped; properties "class", "pixels" and "area".  No "crs" member is written: the
-coordinates are in the raster's own coordinate reference system."""
+coordinates are in the raster's own coordinate reference system.
+
+--depth_out FILE.tif writes the water depth of the class map as written (after --mmu), computed on the device
+(kurosiwo_amd.scene.flood_depth) as FwDET does (Cohen et al. 2018): the DEM at the shore pixels -- water of --depth_classes (default
+1 2) with a valid dry edge neighbour inside the scene; the scene border and invalid pixels make no shore -- is handed to every water
+pixel from its nearest shore pixel by exact Euclidean distance, wherever in the scene that pixel lies, and the DEM is subtracted,
+clamped at zero.  The DEM is --depth_dem, else the file of --dem; it has the scene's size and is read raw, in metres: its nodata tag
+and NaN become NaN, no gap is filled and nothing is standardised (the model's copy of --dem is another matter).  The raster is a
+float32 Deflate GeoTIFF in tiles of 256 with nodata NaN and the first post file's georeferencing: 0 on dry land, NaN at invalid
+pixels, at water without a DEM value and where the scene has no shore at all.  --report then gains a key "depth": "water_pixels",
+"with_depth" (those with a finite depth), "max" and "mean" over them, and "volume" (their sum in float64 times "pixel_area"; null
+without georeferencing).  FwDET's smoothing filter, cost-distance allocation, depth attributes per polygon and a DEM on another grid
+are outside this tool."""
 import argparse
 import json
 import os
@@ -52,7 +65,7 @@ if ROOT not in sys.path:
 from kurosiwo_amd import geotiff                                            # noqa: E402
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
-from kurosiwo_amd.scene import cd_forward, polygonize, polygons_geojson, predict_scene, seg_forward, sieve      # noqa: E402
+from kurosiwo_amd.scene import cd_forward, flood_depth, polygonize, polygons_geojson, predict_scene, seg_forward, sieve      # noqa: E402
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -85,6 +98,9 @@ parser.add_argument("--sieve_passes", type=int, default=1)
 parser.add_argument("--report", default=None, help="FILE.json: per-class pixel counts and areas of the map as written")
 parser.add_argument("--polygons", default=None, help="FILE.geojson: the components of --polygon_classes of the map as written, as polygons")
 parser.add_argument("--polygon_classes", type=int, nargs="+", default=[1, 2])
+parser.add_argument("--depth_out", default=None, help="FILE.tif: the water depth of the map as written, in the DEM's unit")
+parser.add_argument("--depth_dem", default=None, help="the DEM the depth is taken from, raw, on the scene's grid (default: the file of --dem)")
+parser.add_argument("--depth_classes", type=int, nargs="+", default=[1, 2])
 
 
 def read_date(paths, nodata):
@@ -114,6 +130,17 @@ def read_dem(path):
     return geotiff.fill_nodata(np.ascontiguousarray(a))
 
 
+def read_raw_dem(path):
+    """the DEM for --depth_out: its values as they are, the nodata tag and NaN as NaN; no gap is filled and nothing is standardised"""
+    a, meta = geotiff.read(path, dtype=np.float32, squeeze=False)
+    if a.shape[0] != 1:
+        raise SystemExit(f"predict.py: the DEM has one band, {path} has {a.shape[0]}")
+    a = np.ascontiguousarray(a[0])
+    if meta["nodata"] is not None and not np.isnan(meta["nodata"]):
+        a[a == np.float32(meta["nodata"])] = np.nan
+    return a
+
+
 def load_model(configs, model_configs, checkpoint):
     if configs["task"] == "cd":
         configs["resume_checkpoint"] = checkpoint
@@ -136,6 +163,11 @@ def main(argv=None):
         raise SystemExit("predict.py: --sieve_passes >= 1")
     if any(not 0 <= c <= 62 for c in args.polygon_classes):
         raise SystemExit("predict.py: --polygon_classes takes class values 0 .. 62")
+    if any(not 0 <= c <= 62 for c in args.depth_classes):
+        raise SystemExit("predict.py: --depth_classes takes class values 0 .. 62")
+    depth_dem = args.depth_dem or args.dem
+    if args.depth_out is not None and depth_dem is None:
+        raise SystemExit("predict.py: --depth_out needs a DEM: pass --depth_dem (or --dem)")
     method = args.method.lower()
     task = args.task or ("cd" if method in CD_METHODS else "segmentation")
     dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
@@ -157,6 +189,12 @@ def main(argv=None):
 
     post, post_nd, geo = read_date(args.post, args.nodata)
     pres = [read_date(p, args.nodata) for _, p in dates]
+    raw_dem = None
+    if args.depth_out is not None:
+        raw_dem = read_raw_dem(depth_dem)
+        if raw_dem.shape != post.shape[1:]:
+            raise SystemExit(f"predict.py: the DEM of --depth_out is {raw_dem.shape[0]} x {raw_dem.shape[1]}, the scene {post.shape[1]} x "
+                             f"{post.shape[2]}: a DEM on another grid is not resampled here")
     sar = (list(configs["data_mean"]), list(configs["data_std"]), [configs["clamp_input"]] * len(configs["data_mean"]))
     if task == "cd":                                    # the order of cd_inputs: [date A, date B(, dem)]
         rasters, nodatas = [pres[0][0], post], [pres[0][1], post_nd]
@@ -196,14 +234,26 @@ def main(argv=None):
     geotiff.write(args.out, written, nodata=3, **where)
     print(f"wrote {args.out}: {classes.shape[0]} x {classes.shape[1]} classes" + (
         f", {removed} components below {args.mmu} pixels removed" if args.mmu is not None else ""))
+    scale = geo["pixel_scale"]
+    area = None if scale is None else float(scale[0]) * float(scale[1])
+    depth_report = None
+    if args.depth_out is not None:                      # on the map as written: after --mmu
+        depth = flood_depth(classes, torch.from_numpy(raw_dem).to(dev), water=args.depth_classes, invalid_class=3).cpu().numpy()
+        geotiff.write(args.depth_out, depth, nodata=float("nan"), **where)
+        deep = depth[np.isin(written, args.depth_classes) & np.isfinite(depth)].astype(np.float64)
+        depth_report = {"water_pixels": int(np.isin(written, args.depth_classes).sum()), "with_depth": int(deep.size),
+                        "max": float(deep.max()) if deep.size else None, "mean": float(deep.mean()) if deep.size else None,
+                        "volume": None if area is None else float(deep.sum()) * area}
+        print(f"wrote {args.depth_out}: depth at {depth_report['with_depth']} of {depth_report['water_pixels']} pixels of classes "
+              f"{' '.join(str(c) for c in args.depth_classes)}" + (f", at most {depth_report['max']:.3f}" if deep.size else ""))
     if args.report is not None:
         counts = np.bincount(written.ravel(), minlength=4).tolist()
-        scale = geo["pixel_scale"]
-        area = None if scale is None else float(scale[0]) * float(scale[1])
+        report = {"pixel_counts": counts, "pixel_area": area, "class_area": None if area is None else [area * c for c in counts],
+                  "mmu": args.mmu, "connectivity": args.connectivity, "passes": args.sieve_passes, "components_removed": removed}
+        if depth_report is not None:
+            report["depth"] = depth_report
         with open(args.report, "w") as f:
-            json.dump({"pixel_counts": counts, "pixel_area": area, "class_area": None if area is None else [area * c for c in counts],
-                       "mmu": args.mmu, "connectivity": args.connectivity, "passes": args.sieve_passes, "components_removed": removed}, f,
-                      indent=1)
+            json.dump(report, f, indent=1)
         print(f"wrote {args.report}")
     if args.polygons is not None:
         rings = polygonize(classes, select=args.polygon_classes)

@@ -1,7 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
-                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]]
+                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -32,6 +32,12 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              back to back between two events, at one batch and at all windows of the grid: gather_view and unview per view code (0 .. 3
              index arithmetic, 4 .. 7 through the LDS tile transposer), and ksmi_scene_accumulate_views over 8 views against 8
              ksmi_scene_accumulate launches on the same logits.
+  depth      with --depth (the numbers behind profiles/depth_probe.txt), instead of the passes above: kurosiwo_amd.scene.flood_depth on a
+             size x size class map of three contents -- no water, speckle_scene of tests/sieve_ref.py, one lake (a disc of radius 1500
+             at size 4480, scaled with the size: the longest searches a flood map gives) -- over a smooth synthetic DEM, as the event
+             time of each stage: shore (ksmi_scene_shore and ksmi_scene_select), cols (ksmi_scene_edt_cols), rows (ksmi_scene_edt_rows
+             over the water pixels), depth (ksmi_scene_depth), and their sum; then nearest_feature without `where` on a map whose one
+             feature is pixel (0, 0): every pixel walks out to column 0, the worst case of the outward search (at most 3 repeats).
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -59,7 +65,8 @@ def main():
     ap.add_argument("--polygons", action="store_true", default=False)
     ap.add_argument("--polygons_only", action="store_true", default=False)
     ap.add_argument("--geojson_max_rings", type=int, default=2_000_000)
-    ap.add_argument("--tta", nargs="+", choices=("none", "hflip", "flips", "d4"), default=None)
+    ap.add_argument("--depth", action="store_true", default=False)
+    ap.add_argument("--tta", nargs="+",choices=("none", "hflip", "flips", "d4"), default=None)
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -84,6 +91,9 @@ def main():
             with open(a.out, "a") as f:
                 f.write("\n".join(lines) + "\n")
 
+    if a.depth:
+        depth_probe(a, emit, ev, med)
+        return finish()
     if a.mmu is not None:
         sieve_probe(a, emit, ev, med)
         if a.sieve_only and not a.polygons:
@@ -318,6 +328,77 @@ def tta_probe(a, emit, ev, med, forward, rasters, norm, dev_norm, ys, xs, wt, st
     single_us = per_launch_us(lambda: scene_accumulate(lg[0], ys, xs, i0, wt, acc, wsum), 50)
     emit(what="tta_accumulate", windows=n, views=8, accumulate_views_us=one_us, eight_accumulate_launches_us=eight_us,
          one_accumulate_launch_us=single_us, eight_over_one=round(eight_us / one_us, 2))
+
+
+def depth_probe(a, emit, ev, med):
+    """flood_depth on three maps of a.size x a.size, timed per entry point, then nearest_feature on a map with one feature"""
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib, scene
+    from kurosiwo_amd.runtime import stream_ptr
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    S, water, lib, st = a.size, (1, 2), _lib.load(), stream_ptr()
+    mask = sum(1 << c for c in water)
+    yy, xx = np.mgrid[0:S, 0:S]
+    radius = 1500 * S // 4480
+    lake = ((yy - S // 2) ** 2 + (xx - S // 2) ** 2 <= radius * radius).astype(np.uint8)
+    maps = {"no_water": np.zeros((S, S), np.uint8), "speckle": sieve_ref.speckle_scene(4480, S, S), "lake": lake}
+    dem = torch.from_numpy((100.0 + 20.0 * np.sin(yy / 97.0) * np.cos(xx / 131.0)).astype(np.float32)).cuda()
+    del yy, xx, lake
+    ptr = lambda t: t.data_ptr()
+    chk = _lib.check
+    new = lambda dtype: torch.empty((S, S), dtype=dtype, device="cuda")
+    stages = ("shore", "cols", "rows", "depth")
+    for name, m in maps.items():
+        d = torch.from_numpy(m).cuda()
+
+        def one_pass():
+            edge, wet, near_y, dist2, nearest, depth = (new(t) for t in (torch.uint8, torch.uint8, torch.int32, torch.int32, torch.int32,
+                                                                         torch.float32))
+            e = [ev() for _ in range(5)]
+            e[0].record()
+            chk(lib.ksmi_scene_shore(ptr(d), ptr(dem), mask, 3, S, S, ptr(edge), st), "scene_shore")
+            chk(lib.ksmi_scene_select(ptr(d), mask, S * S, ptr(wet), st), "scene_select")
+            e[1].record()
+            chk(lib.ksmi_scene_edt_cols(ptr(edge), S, S, ptr(near_y), st), "scene_edt_cols")
+            e[2].record()
+            chk(lib.ksmi_scene_edt_rows(ptr(near_y), ptr(wet), S, S, ptr(dist2), ptr(nearest), st), "scene_edt_rows")
+            e[3].record()
+            chk(lib.ksmi_scene_depth(ptr(d), ptr(dem), ptr(nearest), mask, 3, S * S, ptr(depth), None, st), "scene_depth")
+            e[4].record()
+            torch.cuda.synchronize()
+            return [e[j].elapsed_time(e[j + 1]) for j in range(4)], depth, dist2, int(edge.sum())
+        _, first, dist2, shore_pixels = one_pass()                             # warm-up
+        whole = scene.flood_depth(d, dem, water)
+        assert torch.equal(first.view(torch.int32), whole.view(torch.int32))   # the staged sequence is flood_depth
+        runs = [one_pass() for _ in range(a.repeats)]
+        assert torch.equal(first.view(torch.int32), runs[-1][1].view(torch.int32))      # equal bits
+        t = [med(r[0][j] for r in runs) for j in range(4)]
+        wet = (d == 1) | (d == 2)
+        far = int(dist2[wet & (dist2 < scene.EDT_FAR)].max()) if shore_pixels else None
+        emit(what="depth", content=name, size=S, water_pixels=int(wet.sum()), shore_pixels=shore_pixels, largest_dist2=far,
+             **{k + "_ms": round(v, 3) for k, v in zip(stages, t)}, total_ms=round(sum(t), 3), mpixels_per_s=round(S * S / sum(t) * 1e-3, 1))
+        del runs, first, whole, dist2
+    one = torch.zeros((S, S), dtype=torch.uint8, device="cuda")
+    one[0, 0] = 1                                                              # every pixel walks out to column 0: the longest search
+
+    def transform():
+        e = [ev() for _ in range(3)]
+        e[0].record()
+        near_y = scene.nearest_feature_columns(one)
+        e[1].record()
+        dist2, nearest = scene.nearest_feature_rows(near_y)
+        e[2].record()
+        torch.cuda.synchronize()
+        return [e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])], dist2, nearest
+    _, dist2, nearest = transform()                                            # warm-up
+    ramp = torch.arange(S, device="cuda", dtype=torch.int32) ** 2
+    assert torch.equal(dist2, ramp[:, None] + ramp[None, :]) and not bool(nearest.any())
+    runs = [transform()[0] for _ in range(min(a.repeats, 3))]
+    cols, rows = (med(r[j] for r in runs) for j in range(2))
+    emit(what="nearest_feature", content="single_feature_at_0_0", size=S, cols_ms=round(cols, 3), rows_ms=round(rows, 3),
+         total_ms=round(cols + rows, 3), mpixels_per_s=round(S * S / (cols + rows) * 1e-3, 1))
 
 
 def sieve_probe(a, emit, ev, med):
