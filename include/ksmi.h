@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define KSMI_ABI_VERSION 8   /* 8: the stream-ordering state of a step has one owner (ksmi_runner_order, _fork_side, _mark_side, _wait_side); 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list; later, backward-compatible: the dice / Lovasz / focal losses ksmi_seg_loss_workspace, _forward, _backward); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
+#define KSMI_ABI_VERSION 8   /* 8: the stream-ordering state of a step has one owner (ksmi_runner_order, _fork_side, _mark_side, _wait_side; later, backward-compatible: ksmi_conv_wgrad_dispatch_info); 7: round 6 (ksmi_set_knob, ksmi_conv_dispatch_info, ksmi_argmax_confusion_grouped, ksmi_run_list; later, backward-compatible: the dice / Lovasz / focal losses ksmi_seg_loss_workspace, _forward, _backward); 6: round 5 (ksmi_adam_step_mirror, ksmi_maxpool3x3s2_forward_idx / _backward_idx, ksmi_conv_wgrad_fuses_bias == 2: partial bias rows in ksmi_wgrad_desc.bias_grad, hbm probe window bits); 5: round 4 (BatchNorm statistics finished inside the consuming pass: ksmi_bn_fin_*, ksmi_bn*_bwd_fin_*); 2: round 2 (stats_rows, stochastic layers, bias_grad in ksmi_wgrad_desc, ...); 3: round 3 (gate epilogue, ksmi_desc_size); 4: first conv on raw tiles, tile reader, BIT token path */
 #define KSMI_F32 0
 #define KSMI_BF16 1
 #define KSMI_E_ARG (-1)
@@ -197,6 +197,7 @@ int ksmi_conv_forward(const ksmi_conv_desc* d, int dtype, void* stream);
  * generation (4 = persistent long-K igemm4, 3 = persistent short-K igemm3, 2 = igemm2, 1 = first generation), info[1] = 1 when the chosen
  * launcher has a compiled instance for the geometry it picked, igemm4: info[2..7] = WM, NF, waves, schedule, gx, gy.  `info`: 8 ints. */
 int ksmi_conv_dispatch_info(const ksmi_conv_desc* d, int dtype, int32_t* info);
+/* (the weight gradient's hook, ksmi_conv_wgrad_dispatch_info, follows its descriptor below) */
 
 /* Weight packing fp32 parameter -> `dtype` [nchunks][taps][Npad][chunk_elems].
  * element (chunk, tap, j, kk) = w[ k*sK + (j % n_mod)*sN + (j / n_mod)*sD + tap'*sT ],
@@ -253,6 +254,14 @@ typedef struct ksmi_wgrad_desc {
 size_t ksmi_conv_wgrad_workspace(const ksmi_wgrad_desc* d, int dtype);
 int ksmi_conv_wgrad(const ksmi_wgrad_desc* d, int dtype, void* stream);
 int ksmi_conv_wgrad_fuses_bias(const ksmi_wgrad_desc* d, int dtype);
+/* (ABI 8, additive; host only) what ksmi_conv_wgrad(d, dtype) starts, decided without launching; the plans read nsplit here.
+ * `info`: 8 ints.  info[0] = core (1 = first-generation patch kernel, 2 = first-generation token GEMM, 3 = token GEMM of gemm2,
+ * 4 = wgrad3), info[1] = reducer of the partial slabs (0 = none: the core writes the gradient, 1 = wgrad3_reduce_kernel,
+ * 2 = wgrad_reduce_kernel, 3 = tn_reduce_tr_kernel, 4 = tn_reduce_kernel), info[2] = nsplit (what ksmi_conv_wgrad checks d->nsplit
+ * against; ksmi_conv_wgrad_workspace = nsplit slabs), info[3] = what the core does with a non-null bias_grad (0 / 1 / 2 as above:
+ * ksmi_conv_wgrad_fuses_bias answers the same unless KSMI_NO_FUSED_BIAS_GRAD is set), info[4] = B-side tile (core 3) or 16-column
+ * fragments per workgroup (core 1), info[5..7] = 0. */
+int ksmi_conv_wgrad_dispatch_info(const ksmi_wgrad_desc* d, int dtype, int32_t* info);
 
 /* First-layer 3x3 conv on the raw image (NCHW fp32, Cin <= 8 -> Cout = 32*k):
  * models/snunet.py:75 conv0_0.conv1.  Forward writes NHWC `dtype` + BN partial stats;

@@ -121,6 +121,7 @@ SIGNATURES = {
     "ksmi_conv_wgrad_workspace": (_sz, [C.POINTER(WgradDesc), _i]),
     "ksmi_conv_wgrad": (_i, [C.POINTER(WgradDesc), _i, _vp]),
     "ksmi_conv_wgrad_fuses_bias": (_i, [C.POINTER(WgradDesc), _i]),
+    "ksmi_conv_wgrad_dispatch_info": (_i, [C.POINTER(WgradDesc), _i, C.POINTER(C.c_int32)]),
     "ksmi_conv_stats_rows": (_i, [C.POINTER(ConvDesc), _i]),
     "ksmi_conv_gate_supported": (_i, [C.POINTER(ConvDesc), _i]),
     "ksmi_desc_size": (C.c_size_t, [_i]),

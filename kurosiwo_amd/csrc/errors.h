@@ -41,7 +41,10 @@ int ksmi_attn_mfma_sr(int backward, const void* q, const void* kv, void* out, fl
                       void* workspace, int B, int Nq, int Nk, int H, int C, float scale, uint32_t drop_thr, float drop_inv,
                       uint32_t drop_site, const uint32_t* rng, void* stream);
 
-// gemm2.hip: LDS-DMA token GEMMs; 0 = launched, 1 = shape not covered (fall back to gemm.hip), < 0 = error
+// gemm2.hip: LDS-DMA token GEMMs.  Every launcher returns 0, a NEGATIVE KSMI_E_* code or the POSITIVE hipError_t of ksmi_check_launch.
+// ksmi_gemm2_nt / _nn also answer 1 for "shape not covered" (gemm.hip then runs its own kernel); 1 is hipErrorInvalidValue as well, so
+// a caller of those two cannot tell a refused launch from a shape to fall back on.  ksmi_gemm2_tn has no such answer: it is called
+// only after ksmi_gemm2_tn_enabled said yes (wgrad_route, conv_api.hip), and what it returns is the status of the weight gradient.
 int ksmi_gemm2_nt(const void* x, int x_rs, const void* w, int w_rs, const float* bias, const void* resid, int r_rs, void* y, int y_rs,
                   int rows, int K, int N, hipStream_t st);
 int ksmi_gemm2_nn(const void* dy, int dy_rs, const void* w, int w_rs, void* dx, int dx_rs, int rows, int K, int N, int accumulate,
@@ -49,4 +52,6 @@ int ksmi_gemm2_nn(const void* dy, int dy_rs, const void* w, int w_rs, void* dx, 
 int ksmi_gemm2_tn(const void* x, int x_rs, const void* dy, int dy_rs, float* slab, int npad, float* grad, int64_t g_rs, int rows, int K, int N,
                   int Kslab, int nsplit, int rows_per_split, int btile, int accumulate, float* bias_grad, int bias_accumulate, hipStream_t st);
 bool ksmi_gemm2_tn_enabled(int K, int N, int rows_per_split);
+// its tile and split cost model: splits, rows per split and B-side tile for `rows` x K (slab rows) x npad; one split only when `plain`
+void ksmi_gemm2_tn_geom(int rows, int K, int npad, bool plain, int* nsplit, int* rows_per_split, int* btile);
 bool ksmi_gemm2_tn_spl(int tiles_times_splits, int steps_per_split);     // gemm2_tn_kernel runs two wave groups per workgroup (SPL = 2)

@@ -617,11 +617,43 @@ bool ksmi_gemm2_tn_enabled(int K, int N, int rows_per_split) {
   return !(off || K % 8 || N % 8 || K < 64 || N < 64 || rows_per_split % 64);
 }
 
+// tile and split choice of the token-GEMM weight gradient (128 A-side columns x `bt` B-side columns per workgroup) for rows x K x npad.
+// direct (one split, row-major gradient, `plain` layers only): A = k, B = n; slabs: A = n, B = k.  Cost = whole rounds of the 256 CUs x
+// 64-row steps (measured: 0.95 us per step for bt = 128, ~0.6 for 64) + per-tile prologue/epilogue, + the slab traffic a split costs
+// (written once, read once by the reducer at ~4 TB/s) and the reducer launch.
+void ksmi_gemm2_tn_geom(int rows, int K, int npad, bool plain, int* nsplit, int* rows_per_split, int* btile) {
+  const int steps_all = (rows + 63) / 64;
+  double best = 1e30; int bs = 1, bt = 128;
+  static const int f_bt = ksmi_knob_int("KSMI_TN_BT", 0), f_s = ksmi_knob_int("KSMI_TN_SPLIT", 0);   // probes
+  for (int b = 128; b >= 64; b -= 32) {
+    if (f_bt && b != f_bt) continue;
+    const double step_us = b == 128 ? 0.95 : b == 96 ? 0.78 : 0.6;
+    for (int s = 1; s <= 256 && s <= steps_all; s = s < 8 ? s + 1 : s * 2) {
+      if (s == 1 && !plain) continue;
+      if (f_s && s != f_s) continue;
+      // A-side tiles x B-side tiles (direct: A = k; slabs: A = n)
+      const int acols = s == 1 ? K : npad, bcols = s == 1 ? npad : K;
+      const int tiles = ((acols + 127) / 128) * ((bcols + b - 1) / b);
+      const int steps = (steps_all + s - 1) / s;
+      const int rounds = (tiles * s + 255) / 256;
+      // a workgroup that would be alone on its CU runs as two wave groups on half the steps each (gemm2_tn_kernel SPL = 2): measured
+      // with two co-resident half-range workgroups, a step of the pair costs ~0.73 of two serial ones
+      const bool spl = ksmi_gemm2_tn_spl(tiles * s, steps);
+      double t = rounds * ((spl ? 0.73 : 1.0) * steps * step_us + (spl ? 4.0 : 3.0));
+      if (s > 1) t += 2.0 * s * (double)K * npad * 4.0 / 4.0e6 + 3.0 + 0.08 * (s > 16 ? 16 + (s - 16) / 8 : s);   // + the reducer's serial slab walk
+      if (t < best) { best = t; bs = s; bt = b; }
+    }
+  }
+  *btile = bt;
+  *rows_per_split = ((steps_all + bs - 1) / bs) * 64;
+  *nsplit = (rows + *rows_per_split - 1) / *rows_per_split;
+}
+
 // weight gradient of a plain nn.Linear: x [rows][K] (row stride x_rs), dy [rows][N]; `slab` = split partial sums [nsplit][K][Npad]
-// (n contiguous: the layout of tn_reduce_kernel), or nsplit = 1 and grad [N][g_rs] written directly.  0 launched / 1 not covered
+// (n contiguous: the layout of tn_reduce_kernel), or nsplit = 1 and grad [N][g_rs] written directly.  Only for shapes that
+// ksmi_gemm2_tn_enabled accepts: the caller (wgrad_route, conv_api.hip) asks before it chooses this core; the return value is a status
 int ksmi_gemm2_tn(const void* x, int x_rs, const void* dy, int dy_rs, float* slab, int npad, float* grad, int64_t g_rs, int rows, int K, int N,
                   int Kslab, int nsplit, int rows_per_split, int btile, int accumulate, float* bias_grad, int bias_accumulate, hipStream_t st) {
-  if (!ksmi_gemm2_tn_enabled(K, N, rows_per_split)) return 1;
   const unsigned char* const zero_page = gemm2_zero();
   if (!zero_page) return ksmi_fail(KSMI_E_UNSUPPORTED, "gemm2: zero page");
   Gemm2T p = {};

@@ -1,5 +1,5 @@
-// Implicit-GEMM convolution family for gfx950 (MFMA 16x16, LDS-staged halo tiles,
-// virtual concat).  See include/ksmi.h for the C-ABI and DESIGN.md for the tiling.
+// First-generation implicit-GEMM convolution kernels for gfx950 (MFMA 16x16, LDS-staged halo tiles, virtual concat), the slab
+// reducers and the weight packs.  Launch functions: igemm1.h; conv_api.hip decides which descriptors come here.  Tiling: DESIGN.md.
 //
 //   M = output pixels of one TH x TW patch (<= 256, 4 waves x 4 M-fragments x 16)
 //   N = output channels (BN = 16*NT per workgroup)
@@ -11,9 +11,7 @@
 #include "../../include/ksmi.h"
 #include "errors.h"
 #include "igemm_epilogue.h"
-#include "wgrad3.h"
-#include "igemm3.h"
-#include "igemm4.h"
+#include "igemm1.h"
 
 namespace {
 
@@ -780,157 +778,8 @@ __global__ __launch_bounds__(256) void tn_reduce_tr_kernel(const float* __restri
   }
 }
 
-static bool wgrad_generic_forced() { static const bool on = ksmi_knob_is_set("KSMI_WGRAD_GENERIC"); return on; }
-// eligibility of the token-GEMM path and its split geometry
-static bool gemm_tn_eligible(const ksmi_wgrad_desc* d, int es) {
-  return es == 2 && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->nsrc == 1 && d->src[0].scale == nullptr &&
-         d->Hin == d->Hout && d->Win == d->Wout && (d->src[0].c_len % 8) == 0 && (d->N % 8) == 0 && d->N >= 64 && d->src[0].c_len >= 64 &&
-         !wgrad_generic_forced();
-}
-// tile and split choice of the token-GEMM weight gradient (gemm2.hip: 128 A-side columns x `bt` B-side columns per workgroup).
-// direct (one split, row-major gradient): A = k, B = n; slabs: A = n, B = k.  Cost = whole rounds of the 256 CUs x 64-row steps
-// (measured: 0.95 us per step for bt = 128, ~0.6 for 64) + per-tile prologue/epilogue, + the slab traffic a split costs
-// (written once, read once by the reducer at ~4 TB/s) and the reducer launch.
-static void gemm_tn_geom(const ksmi_wgrad_desc* d, int kc, int& nsplit, int& rps, int& tk, int& tn, int& bt) {
-  const int rows = d->B * d->Hout * d->Wout;
-  const int K = d->nchunks * kc;
-  const int npad = (d->N + 15) & ~15;
-  tk = (K + 127) / 128; tn = (npad + 127) / 128;
-  bool plain = d->gK == 1 && (!d->use_tap_off || d->tap_off[0] == 0) && d->gN >= d->src[0].c_len && d->gN < ((int64_t)1 << 31);
-  if (plain && !d->uniform_kc)
-    for (int i = 0; i < d->nchunks; ++i) plain = plain && d->k_off[i] == i * kc;
-  const int steps_all = (rows + 63) / 64;
-  double best = 1e30; int bs = 1; bt = 128;
-  static const int f_bt = ksmi_knob_int("KSMI_TN_BT", 0), f_s = ksmi_knob_int("KSMI_TN_SPLIT", 0);   // probes
-  for (int b = 128; b >= 64; b -= 32) {
-    if (f_bt && b != f_bt) continue;
-    const double step_us = b == 128 ? 0.95 : b == 96 ? 0.78 : 0.6;
-    for (int s = 1; s <= 256 && s <= steps_all; s = s < 8 ? s + 1 : s * 2) {
-      if (s == 1 && !plain) continue;
-      if (f_s && s != f_s) continue;
-      // A-side tiles x B-side tiles (direct: A = k; slabs: A = n)
-      const int acols = s == 1 ? K : npad, bcols = s == 1 ? npad : K;
-      const int tiles = ((acols + 127) / 128) * ((bcols + b - 1) / b);
-      const int steps = (steps_all + s - 1) / s;
-      const int rounds = (tiles * s + 255) / 256;
-      // a workgroup that would be alone on its CU runs as two wave groups on half the steps each (gemm2_tn_kernel SPL = 2): measured
-      // with two co-resident half-range workgroups, a step of the pair costs ~0.73 of two serial ones
-      const bool spl = ksmi_gemm2_tn_spl(tiles * s, steps);
-      double t = rounds * ((spl ? 0.73 : 1.0) * steps * step_us + (spl ? 4.0 : 3.0));
-      if (s > 1) t += 2.0 * s * (double)K * npad * 4.0 / 4.0e6 + 3.0 + 0.08 * (s > 16 ? 16 + (s - 16) / 8 : s);   // + the reducer's serial slab walk
-      if (t < best) { best = t; bs = s; bt = b; }
-    }
-  }
-  rps = ((steps_all + bs - 1) / bs) * 64;
-  nsplit = (rows + rps - 1) / rps;
-}
-
-struct WgradGeom { int taps, kc, nt, bn, patches, pps, nsplit, ntiles, npad; size_t lds; bool tn; int rps, tk, tnn, tbt; bool v3; ksmi_wgrad3_geom_t g3; };
-
 template <typename T>
-WgradGeom wgrad_geom(const ksmi_wgrad_desc* d) {
-  WgradGeom g;
-  g.taps = d->KH * d->KW;
-  g.kc = ElemTraits<T>::kVec * 4;
-  g.npad = (d->N + 15) & ~15;
-  g.nt = g.npad >= 64 ? 4 : (g.npad >= 32 ? 2 : 1);
-  static const int wnt_cap = ksmi_knob_int("KSMI_WGRAD_NT", 4);
-  if (g.nt > wnt_cap) g.nt = wnt_cap;
-  // 3x3 / 4x4: the 64-column tile (96+ accumulators beside the prefetch registers of the patch pipeline) spills at 256 VGPRs and is
-  // latency-starved at 512; two 32-column workgroups re-read X from L2 instead and run the same speed or better
-  static const bool wnt4 = ksmi_knob_is_set("KSMI_WGRAD_NT4");
-  if (g.taps >= 9 && g.nt > 2 && !wnt4) g.nt = 2;
-  g.bn = g.nt * 16;
-  g.ntiles = (g.npad + g.bn - 1) / g.bn;
-  const int tilesX = (d->Wout + d->TW - 1) / d->TW, tilesY = (d->Hout + d->TH - 1) / d->TH;
-  g.patches = d->B * tilesX * tilesY;
-  // aim at ~1024 workgroups in total; at most 512 splits
-  static const int wg_target = ksmi_knob_int("KSMI_WGRAD_WGS", 1024);
-  static const int split_cap = ksmi_knob_int("KSMI_WGRAD_SPLITS", 512);   // single-chunk gradients (K <= 32) otherwise run one workgroup per CU
-  int want = wg_target / (d->nchunks * g.ntiles);
-  if (want < 1) want = 1;
-  if (want > split_cap) want = split_cap;
-  if (want > g.patches) want = g.patches;
-  g.pps = (g.patches + want - 1) / want;
-  g.nsplit = (g.patches + g.pps - 1) / g.pps;
-  const int HH = (d->TH - 1) * d->stride + d->KH, HW = (d->TW - 1) * d->stride + d->KW;
-  const int P = d->TH * d->TW, Ppad = (P + g.kc - 1) / g.kc * g.kc;
-  g.lds = ((HH * HW * 64 + 255) & ~255) + (size_t)Ppad * g.bn * sizeof(T);
-  if (g.taps == 1 && g.lds < (size_t)(g.kc / 16) * g.nt * 4096) g.lds = (size_t)(g.kc / 16) * g.nt * 4096;   // split-k reduction buffer
-  g.tn = gemm_tn_eligible(d, (int)sizeof(T));
-  if (g.tn) gemm_tn_geom(d, g.kc, g.nsplit, g.rps, g.tk, g.tnn, g.tbt);
-  // 3x3 stride-1 bf16 gradients with whole 32-channel chunks: channel-owner kernel (wgrad3.hip), same slab layout and reducer
-  g.v3 = !g.tn && ksmi_wgrad3_geom(d, sizeof(T) == 2 ? KSMI_BF16 : KSMI_F32, &g.g3);
-  if (g.v3) g.nsplit = g.g3.nsplit;
-  return g;
-}
-
-// KSMI_SLAB_BIAS=0: the split-mode token weight gradient leaves the bias gradient to a channel_sum pass (the round-4 route; same-box A/B)
-static bool wgrad_slab_bias_on() {
-  static const bool on = (ksmi_knob_int("KSMI_SLAB_BIAS", 1) != 0);
-  return on;
-}
-
-template <typename T>
-int launch_wgrad(const ksmi_wgrad_desc* d, hipStream_t st) {
-  WgradGeom g = wgrad_geom<T>(d);
-  if (d->TH * d->TW > 256) return ksmi_fail(KSMI_E_ARG, "wgrad: patch too large");
-  if (d->nsplit != g.nsplit) return ksmi_fail(KSMI_E_ARG, "wgrad: nsplit does not match ksmi_conv_wgrad_workspace geometry");
-  if (g.v3) {
-    int rc3 = ksmi_wgrad3_launch(d, &g.g3, st);
-    if (rc3) return rc3;
-    return ksmi_wgrad3_reduce(d, &g.g3, st);
-  }
-  if (g.tn) {
-    // plain row-major nn.Linear gradient (unit K stride, one tap at offset 0, contiguous k rows)
-    bool plain = d->gK == 1 && (!d->use_tap_off || d->tap_off[0] == 0) && d->gN >= d->src[0].c_len && d->gN < ((int64_t)1 << 31);
-    if (plain && !d->uniform_kc)
-      for (int i = 0; i < d->nchunks; ++i) plain = plain && d->k_off[i] == i * g.kc;
-    {
-      const int rows = d->B * d->Hout * d->Wout;
-      const bool direct = plain && g.nsplit == 1;
-      // bias_grad: the final gradient in direct mode; in slab mode (plain layers only) the partial column sums of dY per split,
-      // [nsplit][N] (ksmi_conv_wgrad_fuses_bias == 2: the caller sums the rows)
-      const int r2 = ksmi_gemm2_tn((const bf16_t*)d->src[0].ptr + d->src[0].c_off, d->src[0].C, (const bf16_t*)d->dy + d->dy_c_off, d->dyC, d->partial,
-                                   g.npad, direct ? d->grad : nullptr, d->gN, rows, d->src[0].c_len, d->N, d->nchunks * g.kc, g.nsplit, g.rps,
-                                   g.tbt, d->accumulate, (direct || (plain && wgrad_slab_bias_on())) ? d->bias_grad : nullptr, d->bias_accumulate, st);
-      if (r2 < 0) return r2;
-      if (r2 == 0) {
-        if (direct) return 0;
-        if (g.nsplit > 16) {      // many thin slabs (small matrices): the 8-lanes-per-element tree reducer hides the slab walk better
-          const size_t totalr = (size_t)d->nchunks * g.kc * g.npad;
-          int blocksr = (int)((totalr * 8 + 255) / 256); if (blocksr > 4096) blocksr = 4096;
-          hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocksr), dim3(256), 0, st, *d, 1, g.kc);
-          return ksmi_check_launch("wgrad_reduce");
-        }
-        static const int tr_on = ksmi_knob_int("KSMI_TN_REDUCE_TR", 1);      // 0: the element-wise reducer (round 1)
-        if (tr_on && plain) {
-          const int Kreal = d->uniform_kc ? d->k_total : d->k_off[d->nchunks - 1] + d->k_len[d->nchunks - 1];
-          const dim3 gridr((g.npad + 31) / 32, (Kreal + 31) / 32);
-          hipLaunchKernelGGL(tn_reduce_tr_kernel, gridr, dim3(256), 0, st, d->partial, g.nsplit, (size_t)d->nchunks * g.kc * g.npad, g.npad, d->N, Kreal,
-                             d->grad, d->gN, d->accumulate);
-          return ksmi_check_launch("tn_reduce_tr");
-        }
-        const size_t total0 = (size_t)d->nchunks * g.kc * g.npad / 4;
-        int blocks0 = (int)((total0 + 255) / 256); if (blocks0 > 8192) blocks0 = 8192;
-        hipLaunchKernelGGL(tn_reduce_kernel, dim3(blocks0), dim3(256), 0, st, *d, g.kc, d->nchunks * g.kc);
-        return ksmi_check_launch("tn_reduce");
-      }
-    }
-    hipLaunchKernelGGL(gemm_tn_wgrad_kernel, dim3(g.tk, g.tnn, g.nsplit), dim3(256), 0, st, *d, d->B * d->Hout * d->Wout, g.rps, d->nchunks * g.kc);
-    int rc0 = ksmi_check_launch("gemm_tn_wgrad");
-    if (rc0) return rc0;
-    if (g.nsplit > 16) {      // many thin slabs (small matrices): the 8-lanes-per-element tree reducer hides the slab walk better
-      const size_t totalr = (size_t)d->nchunks * g.kc * g.npad;
-      int blocksr = (int)((totalr * 8 + 255) / 256); if (blocksr > 4096) blocksr = 4096;
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocksr), dim3(256), 0, st, *d, 1, g.kc);
-      return ksmi_check_launch("wgrad_reduce");
-    }
-    const size_t total0 = (size_t)d->nchunks * g.kc * g.npad / 4;
-    int blocks0 = (int)((total0 + 255) / 256); if (blocks0 > 8192) blocks0 = 8192;
-    hipLaunchKernelGGL(tn_reduce_kernel, dim3(blocks0), dim3(256), 0, st, *d, g.kc, d->nchunks * g.kc);
-    return ksmi_check_launch("tn_reduce");
-  }
+int launch_wgrad_patch(const ksmi_wgrad_desc* d, const ksmi_igemm1_wgeom_t& g, hipStream_t st) {
   {   // per-lane offsets of the staging loads are 32-bit
     const size_t pin = d->in_sy ? (size_t)d->B * d->in_H * d->in_W : (size_t)d->B * d->Hin * d->Win;
     size_t cmax = d->dyC;
@@ -968,104 +817,17 @@ int launch_wgrad(const ksmi_wgrad_desc* d, hipStream_t st) {
   else return ksmi_fail(KSMI_E_UNSUPPORTED, "wgrad: kernel size not supported");
 #undef KSMI_DISPATCH_WNT
 #undef KSMI_LAUNCH_WG
-  int rc = ksmi_check_launch("igemm_wgrad");
-  if (rc) return rc;
-  const size_t total = (size_t)g.taps * d->nchunks * g.kc * g.npad;
-  int blocks = (int)((total * 8 + 255) / 256); if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, *d, g.taps, g.kc);
-  return ksmi_check_launch("wgrad_reduce");
+  return ksmi_check_launch("igemm_wgrad");
 }
 
 }  // namespace
 
+// ---- the launch functions of igemm1.h: no decisions here beyond a kernel's own instance table ----------------------------------
+int ksmi_igemm1_forward(const ksmi_conv_desc* d, int dtype, hipStream_t st) {
+  return dtype == KSMI_BF16 ? launch_fwd<bf16_t>(d, st) : launch_fwd<float>(d, st);
+}
+
 extern "C" {
-
-int ksmi_chunk_elems(int dtype) { return dtype == KSMI_BF16 ? 32 : 16; }
-
-int ksmi_conv_grid_m(const ksmi_conv_desc* d) {
-  const int tilesX = (d->Wout + d->TW - 1) / d->TW, tilesY = (d->Hout + d->TH - 1) / d->TH;
-  return d->B * tilesX * tilesY;
-}
-
-size_t ksmi_desc_size(int which) {
-  switch (which) {
-    case 0: return sizeof(ksmi_conv_desc);
-    case 1: return sizeof(ksmi_wgrad_desc);
-    case 2: return sizeof(ksmi_pack_desc);
-    case 3: return sizeof(ksmi_rowsum_desc);
-    case 4: return sizeof(ksmi_tiff_info);
-    default: return 0;
-  }
-}
-
-int ksmi_conv_gate_supported(const ksmi_conv_desc* d, int dtype) {
-  if (!d) return 0;
-  ksmi_conv_desc c = *d;
-  if (!c.stats) c.stats = (float*)(uintptr_t)16;
-  if (!c.gate_src) { c.gate_src = (const void*)(uintptr_t)16; c.xhat_src = c.gate_src; c.g_mean = (const float*)(uintptr_t)16; c.g_rstd = c.g_mean; }
-  ksmi_igemm4_geom_t g4;
-  return ksmi_igemm4_geom(&c, dtype, &g4) ? 1 : 0;
-}
-
-int ksmi_conv_stats_rows(const ksmi_conv_desc* d, int dtype) {
-  if (!d) return 0;
-  ksmi_conv_desc c = *d;
-  if (!c.stats) c.stats = (float*)(uintptr_t)16;     // the answer is for the launch WITH statistics
-  ksmi_igemm3_geom_t g3;
-  if (!c.gate_src && ksmi_igemm3_geom(&c, dtype, &g3)) return g3.gx;
-  ksmi_igemm4_geom_t g4;
-  if (ksmi_igemm4_geom(&c, dtype, &g4)) return g4.gx;
-  return ksmi_conv_grid_m(d);
-}
-
-// Which kernel ksmi_conv_forward(d, dtype) starts, decided on the host (nothing is launched): info[0] = kernel generation (4 igemm4, 3 igemm3,
-// 2 igemm2, 1 first generation), info[1] = 1 when that launcher has an instantiated kernel for the geometry it chose (a geometry function
-// that accepts a descriptor its launcher cannot start makes the forward raise instead of falling through: ADVICE round 5), igemm4 only:
-// info[2..7] = WM, NF, waves per workgroup, schedule (0 row steps, 1 deep ring, 2 chunk), gx, gy.  Test / tooling hook.
-int ksmi_conv_dispatch_info(const ksmi_conv_desc* d, int dtype, int32_t* info) {
-  if (!d || !info) return ksmi_fail(KSMI_E_ARG, "conv_dispatch_info: null argument");
-  for (int i = 0; i < 8; ++i) info[i] = 0;
-  static const bool force_v1 = ksmi_knob_is_set("KSMI_IGEMM_V1");
-  ksmi_igemm3_geom_t g3;
-  if (!force_v1 && !d->gate_src && ksmi_igemm3_geom(d, dtype, &g3) && (d->stats == nullptr || d->stats_rows == g3.gx)) {
-    info[0] = 3; info[1] = 1; info[6] = g3.gx; info[7] = g3.gy;
-    return 0;
-  }
-  ksmi_igemm4_geom_t g4;
-  if (!force_v1 && ksmi_igemm4_geom(d, dtype, &g4) && (d->stats == nullptr || d->stats_rows == g4.gx)) {
-    info[0] = 4; info[1] = ksmi_igemm4_launchable(d, &g4) ? 1 : 0;
-    info[2] = g4.WM; info[3] = g4.NF; info[4] = g4.nwv; info[5] = g4.deep; info[6] = g4.gx; info[7] = g4.gy;
-    return 0;
-  }
-  info[0] = (!force_v1 && ksmi_igemm2_eligible(d, dtype)) ? 2 : 1;
-  info[1] = 1;
-  return 0;
-}
-
-int ksmi_conv_forward(const ksmi_conv_desc* d, int dtype, void* stream) {
-  if (!d || d->nsrc < 1 || d->nsrc > KSMI_MAX_SRC || d->ndst < 1 || d->ndst > KSMI_MAX_SRC || d->nchunks < 1 ||
-      (d->nchunks > KSMI_MAX_CHUNKS && !(d->uniform_kc && d->nsrc == 1)))
-    return ksmi_fail(KSMI_E_ARG, "conv: bad descriptor");
-  if (dtype != KSMI_BF16 && dtype != KSMI_F32) return ksmi_fail(KSMI_E_ARG, "conv: bad dtype");
-  static const bool force_v1 = ksmi_knob_is_set("KSMI_IGEMM_V1");      // A/B switch for profiling
-  {   // short K, bf16: persistent workgroups with register-resident weights (its statistics rows = workgroups, not tiles)
-    ksmi_igemm3_geom_t g3;
-    if (!force_v1 && !d->gate_src && ksmi_igemm3_geom(d, dtype, &g3) && (d->stats == nullptr || d->stats_rows == g3.gx))
-      return ksmi_igemm3_launch(d, &g3, (hipStream_t)stream);
-    // long K, >= 64 output channels, 3x3: persistent workgroups with halo / weight rings (igemm4.hip); same statistics-row rule
-    ksmi_igemm4_geom_t g4;
-    if (!force_v1 && ksmi_igemm4_geom(d, dtype, &g4) && (d->stats == nullptr || d->stats_rows == g4.gx))
-      return ksmi_igemm4_launch(d, &g4, (hipStream_t)stream);
-    if (d->gate_src) return ksmi_fail(KSMI_E_UNSUPPORTED, "conv: the gate epilogue needs the persistent long-K kernel (ksmi_conv_gate_supported)");
-  }
-  if (d->stats && d->stats_rows != 0 && d->stats_rows != ksmi_conv_grid_m(d))
-    return ksmi_fail(KSMI_E_ARG, "conv: stats_rows does not match the kernel this descriptor runs on (set it from ksmi_conv_stats_rows)");
-  if (!force_v1 && ksmi_igemm2_eligible(d, dtype)) return ksmi_igemm2_launch(d, dtype, (hipStream_t)stream);
-  if (d->alpha != 0.f || d->resid || d->relu_out || d->uniform_kc)
-    return ksmi_fail(KSMI_E_UNSUPPORTED, "conv: alpha/resid/relu_out/uniform chunks need whole-chunk sources (igemm2 path)");
-  if (dtype == KSMI_BF16) return launch_fwd<bf16_t>(d, (hipStream_t)stream);
-  return launch_fwd<float>(d, (hipStream_t)stream);
-}
 
 int ksmi_pack_weights(const ksmi_pack_desc* d, int dtype, void* stream) {
   if (!d || d->nchunks < 1 || (d->nchunks > KSMI_MAX_CHUNKS && !d->uniform_kc)) return ksmi_fail(KSMI_E_ARG, "pack: bad descriptor");
@@ -1090,35 +852,70 @@ int ksmi_pack_weights_batched(const ksmi_pack_desc* descs_device, int n, int dty
   return ksmi_check_launch("pack_weights_batched");
 }
 
-size_t ksmi_conv_wgrad_workspace(const ksmi_wgrad_desc* d, int dtype) {
-  WgradGeom g = dtype == KSMI_BF16 ? wgrad_geom<bf16_t>(d) : wgrad_geom<float>(d);
-  // caller reads nsplit back through the returned size: bytes = nsplit * slab
-  return (size_t)g.nsplit * g.taps * d->nchunks * g.kc * g.npad * sizeof(float);
-}
-
-// 1: ksmi_conv_wgrad(d) also writes d->bias_grad (the token-GEMM path of gemm2.hip in its one-split, direct-write mode)
-// 2 (round 5): the split (slab) mode of the same path writes the PARTIAL column sums of dY, one row per split, to d->bias_grad
-//    [d->nsplit][d->N] floats (overwritten, not accumulated); the caller sums the rows into the bias gradient
-int ksmi_conv_wgrad_fuses_bias(const ksmi_wgrad_desc* d, int dtype) {
-  if (!d || dtype != KSMI_BF16 || d->nsrc != 1) return 0;
-  static const bool off = ksmi_knob_is_set("KSMI_NO_FUSED_BIAS_GRAD");
-  if (off) return 0;
-  WgradGeom g = wgrad_geom<bf16_t>(d);
-  if (!g.tn || g.v3) return 0;
-  bool plain = d->gK == 1 && (!d->use_tap_off || d->tap_off[0] == 0) && d->gN >= d->src[0].c_len && d->gN < ((int64_t)1 << 31);
-  if (plain && !d->uniform_kc)
-    for (int i = 0; i < d->nchunks; ++i) plain = plain && d->k_off[i] == i * g.kc;
-  if (!(plain && ksmi_gemm2_tn_enabled(d->src[0].c_len, d->N, g.rps))) return 0;
-  if (g.nsplit == 1) return 1;
-  return wgrad_slab_bias_on() && (g.tbt == 64 || g.tbt == 96 || g.tbt == 128) ? 2 : 0;
-}
-
-int ksmi_conv_wgrad(const ksmi_wgrad_desc* d, int dtype, void* stream) {
-  if (!d || d->nsrc < 1 || d->nsrc > KSMI_MAX_SRC || d->nchunks < 1 || (d->nchunks > KSMI_MAX_CHUNKS && !(d->uniform_kc && d->nsrc == 1)))
-    return ksmi_fail(KSMI_E_ARG, "wgrad: bad descriptor");
-  if (dtype == KSMI_BF16) return launch_wgrad<bf16_t>(d, (hipStream_t)stream);
-  if (dtype == KSMI_F32) return launch_wgrad<float>(d, (hipStream_t)stream);
-  return ksmi_fail(KSMI_E_ARG, "wgrad: bad dtype");
-}
-
 }  // extern "C"
+
+void ksmi_igemm1_wgrad_geom(const ksmi_wgrad_desc* d, int dtype, ksmi_igemm1_wgeom_t* gp) {
+  ksmi_igemm1_wgeom_t& g = *gp;
+  const int es = dtype == KSMI_BF16 ? 2 : 4;
+  g.taps = d->KH * d->KW;
+  g.kc = ksmi_chunk_elems(dtype);
+  g.npad = (d->N + 15) & ~15;
+  g.nt = g.npad >= 64 ? 4 : (g.npad >= 32 ? 2 : 1);
+  static const int wnt_cap = ksmi_knob_int("KSMI_WGRAD_NT", 4);
+  if (g.nt > wnt_cap) g.nt = wnt_cap;
+  // 3x3 / 4x4: the 64-column tile (96+ accumulators beside the prefetch registers of the patch pipeline) spills at 256 VGPRs and is
+  // latency-starved at 512; two 32-column workgroups re-read X from L2 instead and run the same speed or better
+  static const bool wnt4 = ksmi_knob_is_set("KSMI_WGRAD_NT4");
+  if (g.taps >= 9 && g.nt > 2 && !wnt4) g.nt = 2;
+  g.bn = g.nt * 16;
+  g.ntiles = (g.npad + g.bn - 1) / g.bn;
+  const int tilesX = (d->Wout + d->TW - 1) / d->TW, tilesY = (d->Hout + d->TH - 1) / d->TH;
+  g.patches = d->B * tilesX * tilesY;
+  // aim at ~1024 workgroups in total; at most 512 splits
+  static const int wg_target = ksmi_knob_int("KSMI_WGRAD_WGS", 1024);
+  static const int split_cap = ksmi_knob_int("KSMI_WGRAD_SPLITS", 512);   // single-chunk gradients (K <= 32) otherwise run one workgroup per CU
+  int want = wg_target / (d->nchunks * g.ntiles);
+  if (want < 1) want = 1;
+  if (want > split_cap) want = split_cap;
+  if (want > g.patches) want = g.patches;
+  g.pps = (g.patches + want - 1) / want;
+  g.nsplit = (g.patches + g.pps - 1) / g.pps;
+  const int HH = (d->TH - 1) * d->stride + d->KH, HW = (d->TW - 1) * d->stride + d->KW;
+  const int P = d->TH * d->TW, Ppad = (P + g.kc - 1) / g.kc * g.kc;
+  g.lds = ((HH * HW * 64 + 255) & ~255) + (size_t)Ppad * g.bn * es;
+  if (g.taps == 1 && g.lds < (size_t)(g.kc / 16) * g.nt * 4096) g.lds = (size_t)(g.kc / 16) * g.nt * 4096;   // split-k reduction buffer
+}
+
+int ksmi_igemm1_wgrad_patch(const ksmi_wgrad_desc* d, int dtype, const ksmi_igemm1_wgeom_t* g, hipStream_t st) {
+  return dtype == KSMI_BF16 ? launch_wgrad_patch<bf16_t>(d, *g, st) : launch_wgrad_patch<float>(d, *g, st);
+}
+
+int ksmi_igemm1_wgrad_token(const ksmi_wgrad_desc* d, int kc, int rows_per_split, hipStream_t st) {
+  const int K = d->nchunks * kc, npad = (d->N + 15) & ~15;      // 128 x 128 output tiles
+  KSMI_NOTE(gemm_tn_wgrad_kernel);
+  hipLaunchKernelGGL(gemm_tn_wgrad_kernel, dim3((K + 127) / 128, (npad + 127) / 128, d->nsplit), dim3(256), 0, st, *d, d->B * d->Hout * d->Wout, rows_per_split, K);
+  return ksmi_check_launch("gemm_tn_wgrad");
+}
+
+int ksmi_igemm1_reduce(const ksmi_wgrad_desc* d, int reducer, int taps, int kc, hipStream_t st) {
+  const int npad = (d->N + 15) & ~15;
+  const size_t slab = (size_t)taps * d->nchunks * kc * npad;
+  if (reducer == KSMI_RED_TREE) {
+    int blocks = (int)((slab * 8 + 255) / 256); if (blocks > 4096) blocks = 4096;
+    KSMI_NOTE(wgrad_reduce_kernel);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, st, *d, taps, kc);
+    return ksmi_check_launch("wgrad_reduce");
+  }
+  if (reducer == KSMI_RED_TN_TR) {      // token cores only (taps == 1), plain row-major gradient
+    const int Kreal = d->uniform_kc ? d->k_total : d->k_off[d->nchunks - 1] + d->k_len[d->nchunks - 1];
+    const dim3 grid((npad + 31) / 32, (Kreal + 31) / 32);
+    KSMI_NOTE(tn_reduce_tr_kernel);
+    hipLaunchKernelGGL(tn_reduce_tr_kernel, grid, dim3(256), 0, st, d->partial, d->nsplit, slab, npad, d->N, Kreal, d->grad, d->gN, d->accumulate);
+    return ksmi_check_launch("tn_reduce_tr");
+  }
+  if (reducer != KSMI_RED_TN) return ksmi_fail(KSMI_E_ARG, "wgrad: not a slab reducer of igemm.hip");
+  int blocks = (int)((slab / 4 + 255) / 256); if (blocks > 8192) blocks = 8192;
+  KSMI_NOTE(tn_reduce_kernel);
+  hipLaunchKernelGGL(tn_reduce_kernel, dim3(blocks), dim3(256), 0, st, *d, kc, d->nchunks * kc);
+  return ksmi_check_launch("tn_reduce");
+}

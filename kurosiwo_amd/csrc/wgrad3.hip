@@ -501,6 +501,7 @@ bool ksmi_wgrad3_geom(const ksmi_wgrad_desc* d, int dtype, ksmi_wgrad3_geom_t* g
 int ksmi_wgrad3_reduce(const ksmi_wgrad_desc* d, const ksmi_wgrad3_geom_t* g, hipStream_t st) {
   const int ntaps = g->r0 >= 0 ? 4 : 9;
   const size_t total4 = (size_t)ntaps * d->nchunks * 32 * ((d->N + 15) & ~15) / 4;
+  KSMI_NOTE(wgrad3_reduce_kernel);
   hipLaunchKernelGGL(wgrad3_reduce_kernel, dim3((unsigned)((total4 + 15) / 16)), dim3(256), 0, st, *d, g->nsplit, ntaps);
   return ksmi_check_launch("wgrad3_reduce");
 }

@@ -301,7 +301,12 @@ def make_wgrad(srcs, dy, dyC, dy_c_off, N, grad, gK, gN, gT, accumulate, B, Hin,
             d.chunk_src[i], d.chunk_c0[i], d.k_off[i], d.k_len[i] = si, c0, kg, kl
     lib = _lib.load()
     ws = lib.ksmi_conv_wgrad_workspace(C.byref(d), DT[dtype])
-    npad = (N + 15) // 16 * 16
-    slab = (KH * KW) * len(table) * kc * npad * 4
-    d.nsplit = ws // slab
+    d.nsplit = wgrad_dispatch_info(d, dtype)[2]
     return d, ws
+
+
+def wgrad_dispatch_info(d, dtype):
+    """what ksmi_conv_wgrad(d) will start, decided on the host: [core, reducer, nsplit, bias mode, B-side tile or NT, 0, 0, 0] (ksmi.h)"""
+    info = (C.c_int32 * 8)()
+    _lib.check(_lib.load().ksmi_conv_wgrad_dispatch_info(C.byref(d), DT[dtype], info), "conv_wgrad_dispatch_info")
+    return list(info)

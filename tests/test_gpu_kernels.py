@@ -469,3 +469,78 @@ def test_conv_statistics_are_sums_over_the_stored_bf16_values(dev, cfg):
     ref = torch.nn.functional.conv2d(torch.cat([x.to(torch.bfloat16).float() for x in xs], 1).double(), w.to(torch.bfloat16).double(), padding=1)
     r2 = (ref * ref).sum((0, 2, 3))
     assert ((r2.to(dev) - s2).abs() > 2e-5 * s2 + 1e-6).float().mean() >= 0.3
+
+
+# ------------------------------------------------------------------ weight-gradient routes (csrc/conv_api.hip)
+def _route_linear(rows, K, N, k_real=None):
+    def build(dev):
+        from kurosiwo_amd.runtime import SrcSpec, make_wgrad
+        kr = K if k_real is None else k_real
+        x = seeded_tensor(f"route.x{rows}.{K}", (rows, K)).to(dev, torch.bfloat16)
+        dy = seeded_tensor(f"route.dy{rows}.{N}", (rows, N)).to(dev, torch.bfloat16)
+        grads = [torch.full((N, kr), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
+        return [make_wgrad([SrcSpec(x, K, k_real=kr)], dy, N, 0, N, g, 1, kr, 0, 0, 1, rows, 1, rows, 1, 1, 1, 1, 0, torch.bfloat16) for g in grads], grads, (x, dy)
+    return build
+
+
+def _route_conv3x3(B, H, Cin, N):
+    def build(dev):
+        from kurosiwo_amd.runtime import SrcSpec, make_wgrad
+        x = seeded_tensor(f"route.c3x{B}.{H}.{Cin}", (B, H, H, Cin)).to(dev, torch.bfloat16)
+        dy = seeded_tensor(f"route.c3dy{B}.{H}.{N}", (B, H, H, N)).to(dev, torch.bfloat16)
+        grads = [torch.full((N, Cin, 3, 3), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
+        return [make_wgrad([SrcSpec(x, Cin)], dy, N, 0, N, g, 9, Cin * 9, 1, 0, B, H, H, H, H, 3, 3, 1, 1, torch.bfloat16) for g in grads], grads, (x, dy)
+    return build
+
+
+def _route_deconv2x2(B, H, Cin, Cout):
+    def build(dev):
+        from kurosiwo_amd.runtime import SrcSpec, make_wgrad
+        x = seeded_tensor(f"route.d2x{B}.{H}.{Cin}", (B, H, H, Cin)).to(dev, torch.bfloat16)
+        dy = seeded_tensor(f"route.d2dy{B}.{H}.{Cout}", (B, 2 * H, 2 * H, Cout)).to(dev, torch.bfloat16)
+        grads = [torch.full((Cin, Cout, 2, 2), float("nan"), dtype=torch.float32, device=dev) for _ in range(2)]
+        return [make_wgrad([SrcSpec(dy, Cout)], x, Cin, 0, Cin, g, 4, Cout * 4, 1, 0, B, 2 * H, 2 * H, H, H, 2, 2, 2, 0, torch.bfloat16)
+                for g in grads], grads, (x, dy)
+    return build
+
+
+_CORES = {1: "igemm_wgrad_kernel<bf16, {nt}, 2, 2, ", 3: "gemm2_tn_kernel<", 4: "wgrad3_kernel<"}      # (core 2 needs KSMI_GEMM2_TN_OFF)
+_REDUCERS = {1: "wgrad3_reduce_kernel", 2: "wgrad_reduce_kernel", 3: "tn_reduce_tr_kernel", 4: "tn_reduce_kernel"}
+
+
+@pytest.mark.parametrize("name,build,route", [
+    ("wgrad3", _route_conv3x3(1, 12, 32, 32), (4, 1)),
+    ("gemm2 direct", _route_linear(128, 64, 64), (3, 0)),
+    ("gemm2 slabs, transposing reducer", _route_linear(512, 64, 64), (3, 3)),
+    ("gemm2 slabs, tree reducer", _route_linear(3152, 64, 64), (3, 2)),
+    ("gemm2 slabs, element-wise reducer (56 of 64 channels real: not a plain gradient)", _route_linear(128, 64, 64, k_real=56), (3, 4)),
+    ("patch kernel 2 x 2, NT 1", _route_deconv2x2(2, 8, 16, 32), (1, 2, 1)),
+    ("patch kernel 2 x 2, NT 4", _route_deconv2x2(2, 8, 64, 32), (1, 2, 4)),
+])
+def test_weight_gradient_runs_the_route_its_hook_names(dev, name, build, route):
+    """ksmi_conv_wgrad_dispatch_info is truthful: one small descriptor per (core, reducer) pair that is reachable without a knob (picked
+    with the hook on the CPU; `route` = the core, reducer and, for the patch kernel, NT it names); the kernels ksmi_conv_wgrad starts
+    (ksmi_last_kernels) are exactly that core and that reducer, and the same call repeated gives the same bits.  (Numerics: the parity
+    tests of each kernel above and in test_gpu_tokens.py.)"""
+    import ctypes as C
+    from kurosiwo_amd import _lib
+    from kurosiwo_amd.runtime import DT, stream_ptr, wgrad_dispatch_info
+    lib = _lib.load()
+    descs, grads, operands = build(dev)           # (the descriptors hold raw pointers: the operands stay referenced here)
+    info = wgrad_dispatch_info(descs[0][0], torch.bfloat16)
+    assert tuple(info[:2]) == route[:2] and (len(route) < 3 or info[4] == route[2]), (name, info)
+    want = [_CORES[info[0]].format(nt=info[4])] + ([_REDUCERS[info[1]]] if info[1] else [])
+    buf = C.create_string_buffer(4096)
+    for (d, ws), g in zip(descs, grads):
+        assert d.nsplit == info[2]
+        wsb = torch.empty(max(ws, 16), dtype=torch.uint8, device=dev)
+        d.partial = wsb.data_ptr()
+        lib.ksmi_last_kernels(buf, 4096)
+        _lib.check(lib.ksmi_conv_wgrad(C.byref(d), DT[torch.bfloat16], stream_ptr()), name)
+        n = lib.ksmi_last_kernels(buf, 4096)
+        names = buf.value.decode().split(";")
+        assert n == len(names) == len(want), names
+        assert names[0].startswith(want[0]) and names[1:] == want[1:], (names, want)
+        torch.cuda.synchronize()
+    assert not torch.isnan(grads[0]).any()
+    assert torch.equal(grads[0].view(torch.int32), grads[1].view(torch.int32))
