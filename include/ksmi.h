@@ -903,6 +903,39 @@ int ksmi_scene_shore(const unsigned char* classes_u8, const float* dem_f32, int6
  * nearest_i32[p] >= 0, NaN elsewhere.  NaN is 0x7fc00000.  An index not below HW counts as negative.  HW = 0 is a no-op. */
 int ksmi_scene_depth(const unsigned char* classes_u8, const float* dem_f32, const int32_t* nearest_i32, int64_t water_mask, int invalid_class,
                      int64_t HW, float* depth_f32, float* wse_f32, void* stream);
+/* Zonal statistics for the rasters of a scene (csrc/zonal.hip; kurosiwo_amd/scene.py: zonal_stats, component_stats; predict.py
+ * --polygons attributes, --components).  The reference has no counterpart: it never maps a scene.  A reduction of value rasters keyed
+ * by a zone raster: everything accumulated is an integer, or a minimum / maximum under a total order, so the results depend neither
+ * on launch geometry nor on arrival order; tests/zonal_ref.py restates every entry in numpy.  Pixels are p = y * Ws + x, HW = Hs * Ws
+ * <= 2^31 - 1.  The zone of p is zones_i32[p]; p is skipped when that value is outside 0 .. HW - 1 (the rule of
+ * ksmi_scene_component_sizes) or when where_u8 is given and where_u8[p] == 0.  The rows of the tables are the zones with at least one
+ * pixel that is not skipped, in ascending zone id; N is their number.  Scratch is the caller's: 4 B of presence flags and 4 B of
+ * their scan per pixel (and the scratch of ksmi_scan_i32).  Every entry: HW = 0 or N = 0 is a no-op that returns 0; HW < 0, HW >
+ * 2^31 - 1, N < 0, N > HW, B outside 0 .. 8, frac_bits outside 0 .. 30 or a null pointer are KSMI_E_ARG and launch nothing.
+ *   ksmi_scene_zonal_mark: the reference has no counterpart.  present_i32 [HW] is zeroed, then present_i32[z] = 1 for every zone z
+ *   that some pixel which is not skipped has.  where_u8 may be NULL.  Its exclusive scan (ksmi_scan_i32) gives every present zone its
+ *   row, and N. */
+int ksmi_scene_zonal_mark(const int32_t* zones_i32, const unsigned char* where_u8, int64_t HW, int32_t* present_i32, void* stream);
+/* ksmi_scene_zonal_tables: the reference has no counterpart.  row_i32 = the scanned presence flags.  zone_i32[row_i32[z]] = z for
+ * every z with present_i32[z] != 0 and a row below N, and the N rows of the tables take the neutral element of their reduction:
+ * count_i32 [N] = 0; bbox_i32 [N][4] = (2^31 - 1, 2^31 - 1, -1, -1); sum_x_i64 [N] = sum_y_i64 [N] = 0; and for B > 0 valid_i32 [B][N]
+ * = 0, vmin_f32 [B][N] = +inf, vmax_f32 [B][N] = -inf, vsum_i64 [B][N] = 0.  With B = 0 the four band tables may be NULL. */
+int ksmi_scene_zonal_tables(const int32_t* present_i32, const int32_t* row_i32, int64_t HW, int64_t N, int B, int32_t* zone_i32,
+                            int32_t* count_i32, int32_t* bbox_i32, int64_t* sum_x_i64, int64_t* sum_y_i64, int32_t* valid_i32, float* vmin_f32,
+                            float* vmax_f32, int64_t* vsum_i64, void* stream);
+/* ksmi_scene_zonal_accumulate: the reference has no counterpart.  Onto the tables of ksmi_scene_zonal_tables, for every pixel p =
+ * (y, x) that is not skipped, at r = row_i32[zones_i32[p]] (a row not below N addresses nothing): count_i32[r] += 1; bbox_i32[r] =
+ * (min x, min y, max x, max y), inclusive pixel indices; sum_x_i64[r] += x, sum_y_i64[r] += y; and per band b < B with v =
+ * values_f32[b][p] finite (NaN and +-inf are left out): valid_i32[b][r] += 1; vmin_f32[b][r] and vmax_f32[b][r] = the extremes in the
+ * order of the key k = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) compared unsigned, in which -0.0f < +0.0f (the tables hold
+ * float bits whose keys are what is compared); vsum_i64[b][r] += q, q = (int64) rintf(fminf(fmaxf(v, -L), L) * 2^frac_bits), L =
+ * 2^(32 - frac_bits): the product is in fp32 and exact, rintf rounds half to even, |q| <= 2^32, so a sum over 2^31 - 1 pixels fits.
+ * Equal zones are combined along x inside a wave (runs of consecutive lanes, cut at the start of a row), then per workgroup in a
+ * hashed table in LDS (a collision goes straight to global memory), then one global integer atomic per slot and statistic.  The
+ * inputs are left unchanged.  values_f32 may be NULL with B = 0. */
+int ksmi_scene_zonal_accumulate(const int32_t* zones_i32, const unsigned char* where_u8, const float* values_f32, int B, int Hs, int Ws,
+                                int frac_bits, const int32_t* row_i32, int64_t N, int32_t* count_i32, int32_t* bbox_i32, int64_t* sum_x_i64,
+                                int64_t* sum_y_i64, int32_t* valid_i32, float* vmin_f32, float* vmax_f32, int64_t* vsum_i64, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -214,7 +214,10 @@ SIGNATURES = {
     "ksmi_scene_select": (_i, [_vp, _i64, _i64, _vp, _vp]),
     "ksmi_scene_shore": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "ksmi_scene_depth": (_i, [_vp, _vp, _vp, _i64, _i, _i64, _vp, _vp, _vp]),
-    "ksmi_bmm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
+    "ksmi_scene_zonal_mark": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "ksmi_scene_zonal_tables": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ksmi_scene_zonal_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ksmi_bmm_f32":(_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
     "ksmi_softmax_rows_f32": (_i, [_vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_softmax_rows_backward_f32": (_i, [_vp, _vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_semantic_tokens_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

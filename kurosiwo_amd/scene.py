@@ -13,8 +13,12 @@ component; integers throughout, equal to the flood fill of tests/sieve_ref.py.  
 into boundary rings: the boundary edges of the 4-connected components, each with its successor, the rings by pointer doubling, and the
 vertex lists in ring order; `polygons_geojson` writes them as GeoJSON on the host.  `flood_depth` (csrc/depth.hip) turns the class map
 and a DEM into water depth: the shore pixels, the exact Euclidean nearest-feature transform of the shore (`nearest_feature`: a column
-pass and a row pass, integers throughout, equal to tests/depth_ref.py) and one subtraction.  Everything runs on the current stream; nothing
-synchronises but the three counts (edges, rings, vertices) that `polygonize` reads to size its buffers."""
+pass and a row pass, integers throughout, equal to tests/depth_ref.py) and one subtraction.  `zonal_stats` (csrc/zonal.hip) reduces value
+rasters per zone of a zone raster -- pixel count, bounding box, coordinate sums and per band the finite count, the extremes under a
+total order and a fixed-point sum; integers and min / max only, equal to tests/zonal_ref.py -- and `component_stats` keys it by the
+component labels, so that the depth and the scores meet the polygons: `polygons_geojson(..., attributes=)` joins the rows to the
+features by label.  Everything runs on the current stream; nothing synchronises but the three counts (edges, rings, vertices) that
+`polygonize` reads to size its buffers and the one count (zones) that `zonal_stats` reads to size its tables."""
 import gc
 from collections import namedtuple
 
@@ -33,6 +37,9 @@ EDT_FAR = 2 ** 31 - 1             # dist2 where there is no feature, or the pixe
 EDT_COLUMN_TILE = 64              # COL_MIN_TILE of csrc/depth.hip: the rows of a y-tile of the column pass, up to 8192 rows
 EDT_ROW_WINDOW = (256, 896)       # (ROW_TILE, ROW_HALO) of csrc/depth.hip: the pixels of a workgroup, the columns staged either side
 Rings = namedtuple("Rings", "label ring_id start area2 verts")
+MAX_ZONAL_BANDS = 8               # ZN_MAX_B of csrc/zonal.hip
+ZONAL_BLOCK = (4096, 64)          # (ZN_PER_BLOCK, ZN_SLOTS) of csrc/zonal.hip: the pixels of a workgroup, the zones it combines in LDS
+Zonal = namedtuple("Zonal", "zone count bbox sum_x sum_y valid vmin vmax vsum frac_bits")
 SCORES = {None: None, "logits": 0, "softmax": 1}
 # test-time view sets, in ascending code; a code's bit 2 transposes the window (first), bit 1 then flips y, bit 0 then flips x
 VIEW_SETS = {"hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -554,7 +561,24 @@ def polygonize(classes, select=(1, 2), labels=None):
     return Rings(label, ring_id, start, area2, verts)
 
 
-def polygons_geojson(rings, classes, pixel_scale=None, origin=None):
+def zonal_geometry(zonal, pixel_scale=None, origin=None):
+    """(bbox float64 [N, 4], centroid_x float64 [N], centroid_y float64 [N]) of the rows of a Zonal, on the host, in the arithmetic of
+    the vertices of polygons_geojson (ox + x * sx, oy - y * sy; scale (1, 1) and origin (0, 0) without georeferencing): bbox = [west,
+    south, east, north] from the pixel corners x0, y1 + 1, x1 + 1, y0 of the integer bbox; the centroid is the mean pixel centre,
+    (sum_x + count / 2) / count and (sum_y + count / 2) / count in float64, through the same map."""
+    count, box, sum_x, sum_y = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (zonal.count, zonal.bbox, zonal.sum_x, zonal.sum_y))
+    sx, sy = (1.0, 1.0) if pixel_scale is None else (float(pixel_scale[0]), float(pixel_scale[1]))
+    ox, oy = (0.0, 0.0) if origin is None else (float(origin[0]), float(origin[1]))
+    n = count.astype(np.float64)
+    bbox = np.empty((count.shape[0], 4), np.float64)
+    bbox[:, 0] = ox + box[:, 0].astype(np.float64) * sx
+    bbox[:, 1] = oy - (box[:, 3].astype(np.float64) + 1.0) * sy
+    bbox[:, 2] = ox + (box[:, 2].astype(np.float64) + 1.0) * sx
+    bbox[:, 3] = oy - box[:, 1].astype(np.float64) * sy
+    return bbox, ox + (sum_x.astype(np.float64) + n / 2.0) / n * sx, oy - (sum_y.astype(np.float64) + n / 2.0) / n * sy
+
+
+def polygons_geojson(rings, classes, pixel_scale=None, origin=None, attributes=None):
     """A GeoJSON FeatureCollection (a dict) of the rings of `polygonize`, built on the host.
 
     One Polygon feature per component in ascending label: its exterior ring first, then its holes in ascending ring id, each closed by
@@ -565,7 +589,23 @@ def polygons_geojson(rings, classes, pixel_scale=None, origin=None):
     "class" (the class value of the component), "pixels" (the component's pixel count: the sum of its rings' area2 over 2) and "area"
     (pixels * sx * sy; null without a pixel scale).  No "crs" member is written: the coordinates are in the raster's own coordinate
     reference system, not necessarily the WGS 84 of RFC 7946, and whoever reads the file must know it.  classes: the map the rings
-    were traced on, a tensor or an array."""
+    were traced on, a tensor or an array.
+
+    attributes: None (the output above, byte for byte), a Zonal whose `zone` values are component labels (component_stats), or a pair
+    (Zonal, {property name: one value per row}).  Rows are joined to features by label (both are in ascending label).  A feature
+    with a row gets a GeoJSON "bbox" member [west, south, east, north] (zonal_geometry: the pixel corners of the integer bbox through
+    the vertices' arithmetic), the properties "centroid_x" and "centroid_y" (the mean pixel centre, in map coordinates) and every
+    named property from its row; a feature without a row gets null for all of these properties and no "bbox"."""
+    extra, names, row_of = None, (), {}
+    if attributes is not None:
+        zonal, extra = attributes if isinstance(attributes, tuple) and not hasattr(attributes, "_fields") else (attributes, {})
+        zone = (zonal.zone.cpu().numpy() if torch.is_tensor(zonal.zone) else np.asarray(zonal.zone)).tolist()
+        names = tuple(extra)
+        extra = [v.tolist() if hasattr(v, "tolist") else list(v) for v in extra.values()]
+        if any(len(v) != len(zone) for v in extra):
+            raise ValueError("polygons_geojson: every attribute has one value per row of the Zonal")
+        boxes, cxs, cys = (a.tolist() for a in zonal_geometry(zonal, pixel_scale, origin))
+        row_of = {z: r for r, z in enumerate(zone)}
     label, ring_id, start, area2, verts = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in rings)
     flat = (classes.cpu().numpy() if torch.is_tensor(classes) else np.asarray(classes)).ravel()
     sx, sy = (1.0, 1.0) if pixel_scale is None else (float(pixel_scale[0]), float(pixel_scale[1]))
@@ -591,10 +631,113 @@ def polygons_geojson(rings, classes, pixel_scale=None, origin=None):
             features.append({"type": "Feature",
                              "properties": {"class": int(flat[l]), "pixels": pixels, "area": None if pixel_scale is None else pixels * sx * sy},
                              "geometry": {"type": "Polygon", "coordinates": coords}})
+            if extra is not None:
+                r, props = row_of.get(l), features[-1]["properties"]
+                props["centroid_x"], props["centroid_y"] = (None, None) if r is None else (cxs[r], cys[r])
+                for name, column in zip(names, extra):
+                    props[name] = None if r is None else column[r]
+                if r is not None:
+                    features[-1]["bbox"] = boxes[r]
     finally:
         if collecting:
             gc.enable()
     return {"type": "FeatureCollection", "features": features}
+
+
+# ---------------------------------------------------------------------------------------------------- zonal statistics
+def _check_zonal_values(values, like, frac_bits, name):
+    """values and frac_bits against the map `like`, without a device -> values as [B, Hs, Ws] (or None)"""
+    if isinstance(frac_bits, bool) or not isinstance(frac_bits, (int, np.integer)) or not 0 <= int(frac_bits) <= 30:
+        raise ValueError(f"{name}: frac_bits is an int in 0 .. 30, got {frac_bits!r}")
+    if values is None:
+        return None
+    if not torch.is_tensor(values) or values.dtype != torch.float32 or values.dim() not in (2, 3) or not values.is_contiguous() \
+            or values.shape[-2:] != like.shape or values.device != like.device:
+        raise ValueError(f"{name}: values is a contiguous float32 tensor [B, Hs, Ws] or [Hs, Ws] on the map's device")
+    if values.dim() == 2:
+        values = values.unsqueeze(0)
+    if values.shape[0] > MAX_ZONAL_BANDS:
+        raise ValueError(f"{name}: at most {MAX_ZONAL_BANDS} bands, got {values.shape[0]}")
+    return values
+
+
+def _check_zonal(zones, values, where, frac_bits, name):
+    """the checks that need no device -> values as [B, Hs, Ws] (or None); the caller ends with require_gpu"""
+    if not torch.is_tensor(zones) or zones.dtype != torch.int32 or zones.dim() != 2 or not zones.is_contiguous():
+        raise ValueError(f"{name}: zones is a contiguous int32 device tensor [Hs, Ws]")
+    if zones.numel() > 2 ** 31 - 1:
+        raise ValueError(f"{name}: at most 2^31 - 1 pixels, got {zones.numel()}")
+    values = _check_zonal_values(values, zones, frac_bits, name)
+    if where is not None and (not torch.is_tensor(where) or where.dtype != torch.uint8 or where.shape != zones.shape or not where.is_contiguous()
+                              or where.device != zones.device):
+        raise ValueError(f"{name}: where is a contiguous uint8 tensor [Hs, Ws] on the zones' device")
+    return values
+
+
+def zonal_stats(zones, values=None, where=None, frac_bits=16):
+    """Statistics of value rasters per zone of a zone raster -> Zonal, device tensors.
+
+    zones int32 [Hs, Ws]: the zone of pixel p = y * Ws + x is zones[p]; a value outside 0 .. Hs * Ws - 1 is no zone and the pixel is
+    skipped (the rule of component_sizes), so the labels of label_components are zones as they are.  values: float32 [B, Hs, Ws] or
+    [Hs, Ws], 0 <= B <= 8, or None (geometry only).  where: uint8 [Hs, Ws] or None; a pixel where it is zero is skipped.  One row per
+    zone with at least one pixel that is not skipped, in ascending zone id (N rows):
+      zone         int32 [N]     the zone id
+      count        int32 [N]     its pixels that are not skipped
+      bbox         int32 [N, 4]  (x0, y0, x1, y1), inclusive pixel indices
+      sum_x, sum_y int64 [N]     the sums of the pixel indices x and y: the mean pixel centre is (sum_x + count / 2) / count
+      valid        int32 [B, N]  its pixels whose value in band b is finite
+      vmin, vmax   float32 [B, N] the extremes over the finite values, in the order of the key bits ^ (bits >> 31 ? 0xFFFFFFFF :
+                                 0x80000000) compared unsigned (-0.0 < +0.0); +inf and -inf where valid == 0
+      vsum         int64 [B, N]  the sum over the finite values of q(v) = rint(clamp(v, -2^(32 - frac_bits), 2^(32 - frac_bits)) *
+                                 2^frac_bits), rint to even: |q| <= 2^32, so the sum cannot overflow; the mean is vsum / 2^frac_bits /
+                                 valid in float64 on the host
+    and frac_bits itself.  Everything accumulated is an integer, or a minimum / maximum under a total order: the bits are those of
+    tests/zonal_ref.py on every run.  Launches: the presence flags, their scan, the zone ids and the neutral tables, the accumulate
+    pass (between two small passes that turn the extremes into keys and back).  One integer, N, is read on the host to size the
+    tables.  Scratch: 8 B per pixel (the flags and their scan) and the scan's own 4 B per 2048 pixels; the tables are O(N).  The
+    inputs are left unchanged.  No zone present, or an empty scene: empty tensors; B == 0: the band tables are [0, N]."""
+    values = _check_zonal(zones, values, where, frac_bits, "zonal_stats")
+    require_gpu(zones)
+    dev, HW = zones.device, zones.numel()
+    Hs, Ws = zones.shape
+    B = 0 if values is None else values.shape[0]
+    N = 0
+    lib, st = _lib.load(), stream_ptr()
+    if HW:
+        present = torch.empty(HW, dtype=torch.int32, device=dev)
+        _lib.check(lib.ksmi_scene_zonal_mark(zones.data_ptr(), None if where is None else where.data_ptr(), HW, present.data_ptr(), st),
+                   "scene_zonal_mark")
+        row = torch.empty(HW, dtype=torch.int32, device=dev)
+        N = int(_scan(present, row, "scan_i32").item())                 # the one host read
+    i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
+    i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
+    f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
+    out = Zonal(i32(N), i32(N), i32(N, 4), i64(N), i64(N), i32(B, N), f32(B, N), f32(B, N), i64(B, N), int(frac_bits))
+    if N:
+        band = [t.data_ptr() if B else None for t in (out.valid, out.vmin, out.vmax, out.vsum)]
+        _lib.check(lib.ksmi_scene_zonal_tables(present.data_ptr(), row.data_ptr(), HW, N, B, out.zone.data_ptr(), out.count.data_ptr(),
+                                               out.bbox.data_ptr(), out.sum_x.data_ptr(), out.sum_y.data_ptr(), *band, st), "scene_zonal_tables")
+        _lib.check(lib.ksmi_scene_zonal_accumulate(zones.data_ptr(), None if where is None else where.data_ptr(),
+                                                   values.data_ptr() if B else None, B, Hs, Ws, int(frac_bits), row.data_ptr(), N,
+                                                   out.count.data_ptr(), out.bbox.data_ptr(), out.sum_x.data_ptr(), out.sum_y.data_ptr(), *band, st),
+                   "scene_zonal_accumulate")
+    return out
+
+
+def component_stats(classes, select=(1, 2), values=None, labels=None, frac_bits=16):
+    """zonal_stats over the 4-connected components of the classes in `select` -> Zonal: zones = labels (label_components(classes, 4)
+    unless given), where = select_classes(classes, select).  Its rows are the components `polygonize(classes, select)` emits, in the
+    same order (ascending label; an exterior ring has ring_id == 4 * zone), and count is the feature's "pixels"."""
+    _select_mask(select, "component_stats")
+    if not torch.is_tensor(classes) or classes.dtype != torch.uint8 or classes.dim() != 2 or not classes.is_contiguous():
+        raise ValueError("component_stats: classes is a contiguous uint8 device tensor [Hs, Ws]")
+    if labels is not None and (not torch.is_tensor(labels) or labels.shape != classes.shape or labels.device != classes.device):
+        raise ValueError("component_stats: labels has the shape and the device of classes")
+    _check_zonal_values(values, classes, frac_bits, "component_stats")
+    require_gpu(classes)
+    if labels is None:
+        labels = label_components(classes, 4)
+    return zonal_stats(labels, values, select_classes(classes, select), frac_bits)
 
 
 # ---------------------------------------------------------------------------------------------------- the scene loop

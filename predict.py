@@ -6,7 +6,7 @@
       --out flood.tif [--score softmax --score_out prob.tif] \\
       [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] [--tta hflip] \\
       [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
-      [--polygons flood.geojson --polygon_classes 1 2] \\
+      [--polygons flood.geojson --polygon_classes 1 2] [--components components.csv] \\
       [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2]]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
@@ -38,6 +38,22 @@ units squared; null without georeferencing), "class_area" per class, "mmu", "con
 y negated without one), collinear vertices dropped; properties "class", "pixels" and "area".  No "crs" member is written: the
 coordinates are in the raster's own coordinate reference system.
 
+Every component also carries statistics reduced on the device, keyed by the component labels (kurosiwo_amd.scene.component_stats,
+zonal_stats: integers and key-ordered extremes, the same bits on every run; no raster is read back for them).  --polygons with
+--depth_out: a feature gains "depth_pixels" (its pixels with a finite depth), "depth_max", "depth_mean" (the fixed-point sum of the
+depths at 16 fractional bits / 2^16 / depth_pixels, in float64; both null without such a pixel) and "volume" (that sum / 2^16 *
+"pixel_area"; null without georeferencing).  --polygons with --score softmax: "confidence", the mean over the component of the softmax band of the component's own class (sums at 30 fractional bits; null where
+the class has no band or no finite score); --score logits adds nothing.  A feature that gains any of these also gets a "bbox"
+member [west, south, east, north] (the corners of its pixels' bounding box) and the properties "centroid_x", "centroid_y" (the mean
+pixel centre, in map coordinates); --polygons alone writes what it always wrote.  --components FILE.csv writes the same statistics without the
+polygons, one row per component of --polygon_classes in ascending label (the smallest linear index y * width + x of its pixels); it
+needs neither --polygons nor the GeoJSON writer.  The header row is
+  label,class,pixels,x0,y0,x1,y1,centroid_x,centroid_y
+then ,depth_pixels,depth_max,depth_mean,volume with --depth_out and ,confidence with --score softmax: x0 .. y1 are the inclusive
+pixel indices of the bounding box, floats are written so that they read back to the same float64, and a null is an empty field.
+--report then gains a key "components": "count" (the components of --polygon_classes) and "largest" ({"label", "pixels"} of the one
+with the most pixels, the smallest label on a tie; null without a component); only with --polygons or --components.
+
 --depth_out FILE.tif writes the water depth of the class map as written (after --mmu), computed on the device
 (kurosiwo_amd.scene.flood_depth) as FwDET does (Cohen et al. 2018): the DEM at the shore pixels -- water of --depth_classes (default
 1 2) with a valid dry edge neighbour inside the scene; the scene border and invalid pixels make no shore -- is handed to every water
@@ -47,8 +63,8 @@ and NaN become NaN, no gap is filled and nothing is standardised (the model's co
 float32 Deflate GeoTIFF in tiles of 256 with nodata NaN and the first post file's georeferencing: 0 on dry land, NaN at invalid
 pixels, at water without a DEM value and where the scene has no shore at all.  --report then gains a key "depth": "water_pixels",
 "with_depth" (those with a finite depth), "max" and "mean" over them, and "volume" (their sum in float64 times "pixel_area"; null
-without georeferencing).  FwDET's smoothing filter, cost-distance allocation, depth attributes per polygon and a DEM on another grid
-are outside this tool."""
+without georeferencing).  FwDET's smoothing filter, cost-distance allocation, medians and percentiles per component and a DEM on
+another grid are outside this tool."""
 import argparse
 import json
 import os
@@ -65,7 +81,8 @@ if ROOT not in sys.path:
 from kurosiwo_amd import geotiff                                            # noqa: E402
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
-from kurosiwo_amd.scene import cd_forward, flood_depth, polygonize, polygons_geojson, predict_scene, seg_forward, sieve      # noqa: E402
+from kurosiwo_amd.scene import (cd_forward, component_stats, flood_depth, label_components, polygonize, polygons_geojson, predict_scene,      # noqa: E402
+                                seg_forward, sieve, zonal_geometry)
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -98,6 +115,7 @@ parser.add_argument("--sieve_passes", type=int, default=1)
 parser.add_argument("--report", default=None, help="FILE.json: per-class pixel counts and areas of the map as written")
 parser.add_argument("--polygons", default=None, help="FILE.geojson: the components of --polygon_classes of the map as written, as polygons")
 parser.add_argument("--polygon_classes", type=int, nargs="+", default=[1, 2])
+parser.add_argument("--components", default=None, help="FILE.csv: one row of statistics per component of --polygon_classes of the map as written")
 parser.add_argument("--depth_out", default=None, help="FILE.tif: the water depth of the map as written, in the DEM's unit")
 parser.add_argument("--depth_dem", default=None, help="the DEM the depth is taken from, raw, on the scene's grid (default: the file of --dem)")
 parser.add_argument("--depth_classes", type=int, nargs="+", default=[1, 2])
@@ -139,6 +157,50 @@ def read_raw_dem(path):
     if meta["nodata"] is not None and not np.isnan(meta["nodata"]):
         a[a == np.float32(meta["nodata"])] = np.nan
     return a
+
+
+COMPONENT_COLUMNS = ("label", "class", "pixels", "x0", "y0", "x1", "y1", "centroid_x", "centroid_y")
+DEPTH_COLUMNS = ("depth_pixels", "depth_max", "depth_mean", "volume")
+DEPTH_FRAC_BITS, SCORE_FRAC_BITS = 16, 30
+
+
+def component_table(classes, written, select, depth, score, area, pixel_scale, origin):
+    """the statistics of the components of the classes `select` of the device map `classes` (`written`: its host copy) -> (Zonal,
+    {column: one value per row}): the columns of --components after "label", in order; depth (device float32 [Hs, Ws] or None) adds
+    DEPTH_COLUMNS, score (device softmax [K, Hs, Ws] or None) adds "confidence".  None is a null."""
+    labels = label_components(classes, 4)
+    geom = deep = component_stats(classes, select, values=depth, labels=labels, frac_bits=DEPTH_FRAC_BITS)
+    zone, count, box = geom.zone.cpu().numpy(), geom.count.cpu().numpy(), geom.bbox.cpu().numpy()
+    _, cx, cy = zonal_geometry(geom, pixel_scale, origin)
+    own = written.ravel()[zone].astype(np.int64)
+    cols = {"class": own.tolist(), "pixels": count.tolist(), "x0": box[:, 0].tolist(), "y0": box[:, 1].tolist(), "x1": box[:, 2].tolist(),
+            "y1": box[:, 3].tolist(), "centroid_x": cx.tolist(), "centroid_y": cy.tolist()}
+    if depth is not None:
+        n, top, total = deep.valid[0].cpu().numpy(), deep.vmax[0].cpu().numpy(), deep.vsum[0].cpu().numpy()
+        metres = total / float(2 ** DEPTH_FRAC_BITS)
+        cols["depth_pixels"] = n.tolist()
+        cols["depth_max"] = [float(v) if k else None for v, k in zip(top.tolist(), n.tolist())]
+        cols["depth_mean"] = [m / k if k else None for m, k in zip(metres.tolist(), n.tolist())]
+        cols["volume"] = [None if area is None else m * area for m in metres.tolist()]
+    if score is not None:
+        conf = component_stats(classes, select, values=score, labels=labels, frac_bits=SCORE_FRAC_BITS)
+        n, total = conf.valid.cpu().numpy(), conf.vsum.cpu().numpy()
+        rows = np.arange(zone.size)
+        band = np.minimum(own, score.shape[0] - 1)
+        k = np.where(own < score.shape[0], n[band, rows], 0).tolist()
+        part = (total[band, rows] / float(2 ** SCORE_FRAC_BITS)).tolist()
+        cols["confidence"] = [p / c if c else None for p, c in zip(part, k)]
+    return geom, cols
+
+
+def write_components(path, zonal, cols):
+    """--components: the header row, then one row per component; repr of a float reads back to the same float64, a null is empty"""
+    names = list(cols)
+    cell = lambda v: "" if v is None else repr(v) if isinstance(v, float) else str(v)
+    with open(path, "w") as f:
+        f.write(",".join(["label"] + names) + "\n")
+        for r, z in enumerate(zonal.zone.cpu().numpy().tolist()):
+            f.write(",".join([str(z)] + [cell(cols[k][r]) for k in names]) + "\n")
 
 
 def load_model(configs, model_configs, checkpoint):
@@ -236,9 +298,10 @@ def main(argv=None):
         f", {removed} components below {args.mmu} pixels removed" if args.mmu is not None else ""))
     scale = geo["pixel_scale"]
     area = None if scale is None else float(scale[0]) * float(scale[1])
-    depth_report = None
+    depth_report = depth_dev = None
     if args.depth_out is not None:                      # on the map as written: after --mmu
-        depth = flood_depth(classes, torch.from_numpy(raw_dem).to(dev), water=args.depth_classes, invalid_class=3).cpu().numpy()
+        depth_dev = flood_depth(classes, torch.from_numpy(raw_dem).to(dev), water=args.depth_classes, invalid_class=3)
+        depth = depth_dev.cpu().numpy()
         geotiff.write(args.depth_out, depth, nodata=float("nan"), **where)
         deep = depth[np.isin(written, args.depth_classes) & np.isfinite(depth)].astype(np.float64)
         depth_report = {"water_pixels": int(np.isin(written, args.depth_classes).sum()), "with_depth": int(deep.size),
@@ -246,18 +309,33 @@ def main(argv=None):
                         "volume": None if area is None else float(deep.sum()) * area}
         print(f"wrote {args.depth_out}: depth at {depth_report['with_depth']} of {depth_report['water_pixels']} pixels of classes "
               f"{' '.join(str(c) for c in args.depth_classes)}" + (f", at most {depth_report['max']:.3f}" if deep.size else ""))
+    zonal = cols = None
+    if args.polygons is not None or args.components is not None:        # the statistics stay on the device until the tables are read
+        zonal, cols = component_table(classes, written, args.polygon_classes, depth_dev, score if args.score == "softmax" else None, area,
+                                      geo["pixel_scale"], geo["origin"])
+        assert tuple(["label"] + list(cols)) == COMPONENT_COLUMNS + (DEPTH_COLUMNS if depth_dev is not None else ()) + (
+            ("confidence",) if args.score == "softmax" else ())
+    if args.components is not None:
+        write_components(args.components, zonal, cols)
+        print(f"wrote {args.components}: {zonal.zone.numel()} components of classes {' '.join(str(c) for c in args.polygon_classes)}")
     if args.report is not None:
         counts = np.bincount(written.ravel(), minlength=4).tolist()
         report = {"pixel_counts": counts, "pixel_area": area, "class_area": None if area is None else [area * c for c in counts],
                   "mmu": args.mmu, "connectivity": args.connectivity, "passes": args.sieve_passes, "components_removed": removed}
         if depth_report is not None:
             report["depth"] = depth_report
+        if zonal is not None:
+            sizes, ids = cols["pixels"], zonal.zone.cpu().numpy().tolist()
+            top = int(np.argmax(sizes)) if sizes else None                # the first maximum: the smallest label on a tie
+            report["components"] = {"count": len(ids), "largest": None if top is None else {"label": ids[top], "pixels": sizes[top]}}
         with open(args.report, "w") as f:
             json.dump(report, f, indent=1)
         print(f"wrote {args.report}")
     if args.polygons is not None:
         rings = polygonize(classes, select=args.polygon_classes)
-        collection = polygons_geojson(rings, written, pixel_scale=geo["pixel_scale"], origin=geo["origin"])
+        extra = {k: v for k, v in cols.items() if k in DEPTH_COLUMNS or k == "confidence"}
+        collection = polygons_geojson(rings, written, pixel_scale=geo["pixel_scale"], origin=geo["origin"],
+                                      attributes=(zonal, extra) if extra else None)
         with open(args.polygons, "w") as f:
             json.dump(collection, f)
         print(f"wrote {args.polygons}: {len(collection['features'])} features, {rings.label.numel()} rings of classes "

@@ -1,7 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
-                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth]
+                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth] [--zonal]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -38,6 +38,14 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              time of each stage: shore (ksmi_scene_shore and ksmi_scene_select), cols (ksmi_scene_edt_cols), rows (ksmi_scene_edt_rows
              over the water pixels), depth (ksmi_scene_depth), and their sum; then nearest_feature without `where` on a map whose one
              feature is pixel (0, 0): every pixel walks out to column 0, the worst case of the outward search (at most 3 repeats).
+  zonal      with --zonal (the numbers behind profiles/zonal_probe.txt), instead of the passes above: kurosiwo_amd.scene.zonal_stats keyed by
+             the 4-connectivity labels of a size x size class map, `where` = its classes 1 and 2, of four contents -- one class
+             everywhere (one zone of size^2 pixels: everything the pass combines lands on one row), speckle_scene of
+             tests/sieve_ref.py, one lake (the disc of --depth), a one-pixel checkerboard (every selected pixel its own zone: nothing
+             to combine, the slot table overflows) -- for B = 0, 1 and 4 value bands, as the event time of each stage: mark
+             (ksmi_scene_zonal_mark), scan (ksmi_scan_i32), tables (ksmi_scene_zonal_tables), accumulate (ksmi_scene_zonal_accumulate:
+             keys, the pass, keys back), and their sum; the labels they start from are timed apart.  Next to them, in the same call
+             on the same maps, the event time of flood_depth and of polygonize end to end.
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -66,6 +74,7 @@ def main():
     ap.add_argument("--polygons_only", action="store_true", default=False)
     ap.add_argument("--geojson_max_rings", type=int, default=2_000_000)
     ap.add_argument("--depth", action="store_true", default=False)
+    ap.add_argument("--zonal", action="store_true", default=False)
     ap.add_argument("--tta", nargs="+",choices=("none", "hflip", "flips", "d4"), default=None)
     a = ap.parse_args()
     import numpy as np
@@ -93,6 +102,9 @@ def main():
 
     if a.depth:
         depth_probe(a, emit, ev, med)
+        return finish()
+    if a.zonal:
+        zonal_probe(a, emit, ev, med)
         return finish()
     if a.mmu is not None:
         sieve_probe(a, emit, ev, med)
@@ -399,6 +411,92 @@ def depth_probe(a, emit, ev, med):
     cols, rows = (med(r[j] for r in runs) for j in range(2))
     emit(what="nearest_feature", content="single_feature_at_0_0", size=S, cols_ms=round(cols, 3), rows_ms=round(rows, 3),
          total_ms=round(cols + rows, 3), mpixels_per_s=round(S * S / (cols + rows) * 1e-3, 1))
+
+
+def zonal_probe(a, emit, ev, med):
+    """zonal_stats on four maps of a.size x a.size for B = 0, 1, 4, timed per entry point; flood_depth and polygonize beside them"""
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib, scene
+    from kurosiwo_amd.runtime import stream_ptr
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    S, lib, st = a.size, _lib.load(), stream_ptr()
+    HW = S * S
+    yy, xx = np.mgrid[0:S, 0:S]
+    radius = 1500 * S // 4480
+    lake = ((yy - S // 2) ** 2 + (xx - S // 2) ** 2 <= radius * radius).astype(np.uint8)
+    maps = {"one_class": np.ones((S, S), np.uint8), "speckle": sieve_ref.speckle_scene(4480, S, S), "lake": lake,
+            "checkerboard": ((yy + xx) & 1).astype(np.uint8)}
+    dem = torch.from_numpy((100.0 + 20.0 * np.sin(yy / 97.0) * np.cos(xx / 131.0)).astype(np.float32)).cuda()
+    del yy, xx, lake
+    g = torch.Generator(device="cpu").manual_seed(4480)
+    values = torch.randn((4, S, S), generator=g).cuda()
+    values[1, 100:140, 200:260] = float("nan")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    chk = _lib.check
+    need = int(lib.ksmi_scan_i32_scratch(HW))
+    stages = ("mark", "scan", "tables", "accumulate")
+
+    def timed(fn):
+        e0, e1 = ev(), ev()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    for name, m in maps.items():
+        d = torch.from_numpy(m).cuda()
+        labels_ms = med(timed(lambda: scene.label_components(d, 4))[0] for _ in range(a.repeats + 1))
+        labels, where = scene.label_components(d, 4), scene.select_classes(d, (1, 2))
+        for B in (0, 1, 4):
+            v = values[:B].contiguous() if B else None
+
+            def one_pass():
+                present, row = (torch.empty(HW, dtype=torch.int32, device="cuda") for _ in range(2))
+                total = torch.zeros(1, dtype=torch.int64, device="cuda")
+                scratch = torch.empty(max(need, 1), dtype=torch.int32, device="cuda")
+                e = [ev() for _ in range(5)]
+                e[0].record()
+                chk(lib.ksmi_scene_zonal_mark(ptr(labels), ptr(where), HW, ptr(present), st), "scene_zonal_mark")
+                e[1].record()
+                chk(lib.ksmi_scan_i32(ptr(present), ptr(row), HW, ptr(total), ptr(scratch), need, st), "scan_i32")
+                e[2].record()
+                N = int(total.item())                                          # the one host read: the tables are sized by it
+                i32 = lambda *s: torch.empty(s, dtype=torch.int32, device="cuda")
+                i64 = lambda *s: torch.empty(s, dtype=torch.int64, device="cuda")
+                z = scene.Zonal(i32(N), i32(N), i32(N, 4), i64(N), i64(N), i32(B, N), torch.empty((B, N), device="cuda"),
+                                torch.empty((B, N), device="cuda"), i64(B, N), 16)
+                band = [ptr(t) if B else None for t in (z.valid, z.vmin, z.vmax, z.vsum)]
+                f = [ev() for _ in range(3)]
+                f[0].record()
+                if N:
+                    chk(lib.ksmi_scene_zonal_tables(ptr(present), ptr(row), HW, N, B, ptr(z.zone), ptr(z.count), ptr(z.bbox), ptr(z.sum_x),
+                                                    ptr(z.sum_y), *band, st), "scene_zonal_tables")
+                f[1].record()
+                if N:
+                    chk(lib.ksmi_scene_zonal_accumulate(ptr(labels), ptr(where), ptr(v), B, S, S, 16, ptr(row), N, ptr(z.count), ptr(z.bbox),
+                                                        ptr(z.sum_x), ptr(z.sum_y), *band, st), "scene_zonal_accumulate")
+                f[2].record()
+                torch.cuda.synchronize()
+                return [e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2]), f[0].elapsed_time(f[1]), f[1].elapsed_time(f[2])], z
+            _, first = one_pass()                                              # warm-up
+            whole = scene.zonal_stats(labels, v, where, 16)
+            same = lambda p, q: all(torch.equal(x.view(torch.int32) if x.dtype == torch.float32 else x, y.view(torch.int32) if y.dtype == torch.float32 else y)
+                                    for x, y in zip(p[:-1], q[:-1]))
+            assert same(first, whole)                                          # the staged sequence is zonal_stats
+            runs = [one_pass() for _ in range(a.repeats)]
+            assert same(first, runs[-1][1])                                    # equal bits
+            t = [med(r[0][j] for r in runs) for j in range(4)]
+            emit(what="zonal", content=name, size=S, bands=B, zones=int(first.zone.numel()), largest_zone=int(first.count.max()) if first.zone.numel() else 0,
+                 labels_ms=round(labels_ms, 3), **{k + "_ms": round(x, 3) for k, x in zip(stages, t)}, total_ms=round(sum(t), 3),
+                 mpixels_per_s=round(HW / sum(t) * 1e-3, 1))
+            del runs, first, whole
+        depth_ms = med(timed(lambda: scene.flood_depth(d, dem))[0] for _ in range(a.repeats + 1))
+        polygon_ms = med(timed(lambda: scene.polygonize(d, (1, 2), labels=labels))[0] for _ in range(min(a.repeats, 3) + 1))
+        emit(what="zonal_beside", content=name, size=S, flood_depth_ms=round(depth_ms, 3), polygonize_ms=round(polygon_ms, 3))
+        del d, labels, where
 
 
 def sieve_probe(a, emit, ev, med):
