@@ -936,6 +936,54 @@ int ksmi_scene_zonal_tables(const int32_t* present_i32, const int32_t* row_i32, 
 int ksmi_scene_zonal_accumulate(const int32_t* zones_i32, const unsigned char* where_u8, const float* values_f32, int B, int Hs, int Ws,
                                 int frac_bits, const int32_t* row_i32, int64_t N, int32_t* count_i32, int32_t* bbox_i32, int64_t* sum_x_i64,
                                 int64_t* sum_y_i64, int32_t* valid_i32, float* vmin_f32, float* vmax_f32, int64_t* vsum_i64, void* stream);
+/* Percentiles per zone for the rasters of a scene (csrc/quantile.hip; kurosiwo_amd/scene.py: zonal_quantiles, zonal_sorted,
+ * component_quantiles; predict.py --percentiles).  The reference has no counterpart: it never maps a scene.  A segmented sort of one
+ * float32 value raster keyed by a zone raster, and a selection on the sorted order: integers and bit copies only, so the results
+ * depend neither on launch geometry nor on arrival order; tests/quantile_ref.py restates every entry in numpy.  Pixels, zones, the
+ * skip rule, the rows and N are those of the zonal statistics above: present_i32 is what ksmi_scene_zonal_mark wrote and row_i32 its
+ * exclusive scan.  A pixel takes part when it is not skipped and its value is finite.  Its composite is (row << 32) | k, k = bits ^
+ * (bits >> 31 ? 0xFFFFFFFF : 0x80000000), compared unsigned (-0.0f < +0.0f); every other pixel's composite is all ones, which sorts
+ * last.  Bands go one at a time.  Scratch is the caller's: two buffers of HW composites (16 B per pixel) and
+ * ksmi_scene_quantile_scratch(HW) uint32 counters, beside the 8 B per pixel of flags and rows.  Every entry that launches: HW = 0 or
+ * N = 0 is a no-op that returns 0; HW < 0, HW > 2^31 - 1, N < 0, N > HW, P outside 1 .. 16, a basis point outside 0 .. 10000 or a
+ * null pointer are KSMI_E_ARG and launch nothing.
+ *   ksmi_scene_quantile_passes: the reference has no counterpart.  The radix passes ksmi_scene_quantile_sort runs for N rows: 4 for
+ *   the value field and one per started byte of N - 1, the largest row: 4 for N = 1, never more than 8; 0 for N = 0; -1 for N < 0 or
+ *   N > 2^31 - 1.  After an even number of passes the sorted composites lie in keys_u64, after an odd number in alt_u64. */
+int ksmi_scene_quantile_passes(int64_t N);
+/* ksmi_scene_quantile_scratch: the reference has no counterpart.  The uint32 elements of scratch ksmi_scene_quantile_sort needs for
+ * HW composites: 256 counters per tile of 4096 composites and 256 digit totals; 0 for HW = 0; -1 for HW < 0 or HW > 2^31 - 1. */
+int64_t ksmi_scene_quantile_scratch(int64_t HW);
+/* ksmi_scene_quantile_zones: the reference has no counterpart.  zone_i32[row_i32[z]] = z for every z < HW with present_i32[z] != 0
+ * and a row below N: zone_i32 [N] holds the zone ids in row order (what ksmi_scene_zonal_tables writes, without its tables). */
+int ksmi_scene_quantile_zones(const int32_t* present_i32, const int32_t* row_i32, int64_t HW, int64_t N, int32_t* zone_i32, void* stream);
+/* ksmi_scene_quantile_keys: the reference has no counterpart.  keys_u64 [HW]: the composite of every pixel of the one band
+ * values_f32 [HW], with the row row_i32[zones_i32[p]] (a row not below N takes no part).  where_u8 may be NULL.  The inputs are left
+ * unchanged. */
+int ksmi_scene_quantile_keys(const int32_t* zones_i32, const unsigned char* where_u8, const float* values_f32, const int32_t* row_i32, int64_t HW,
+                             int64_t N, uint64_t* keys_u64, void* stream);
+/* ksmi_scene_quantile_sort: the reference has no counterpart (torch.sort on the composites is the library route the probe times it
+ * against).  Sorts the HW composites of keys_u64 ascending, as unsigned 64-bit integers, with a stable LSD radix sort of 8-bit
+ * digits that alternates between keys_u64 and alt_u64 [HW] (both are overwritten; they must differ): per pass a digit histogram per
+ * tile, a scan over the tiles per digit, a stable scatter (wave64 ballots rank an element among the equal digits of its wave,
+ * per-wave counts in LDS carry the rest); integer LDS atomics only.  The passes are those of ksmi_scene_quantile_passes(N): the bytes
+ * of the row field above the largest row are zero in every composite that takes part and all ones in the others, so they need no
+ * pass; the result lies where that entry says.  scratch_elems < ksmi_scene_quantile_scratch(HW) is KSMI_E_ARG. */
+int ksmi_scene_quantile_sort(uint64_t* keys_u64, uint64_t* alt_u64, int64_t HW, int64_t N, uint32_t* scratch_u32, int64_t scratch_elems,
+                             void* stream);
+/* ksmi_scene_quantile_select: the reference has no counterpart (np.percentile with method "lower" and "higher", the position in
+ * exact arithmetic).  sorted_u64 [HW]: the sorted composites.  The segment of row r lies between the lower bounds of r << 32 and
+ * (r + 1) << 32, found by binary search (one thread per row, the bounds shared by its percentiles); n is its length and
+ * s[0 .. n - 1] its values.  valid_i32 [N] = n.  percentiles_host_i32 [P] is read on the HOST: basis points c, 0 .. 10000.  With pos = c * (n - 1) in int64, k = pos / 10000 and g = pos % 10000:
+ * lower_f32 [P][N] = s[k] and higher_f32 [P][N] = s[k + (g > 0)], bit copies of input values; n = 0 gives NaN (0x7fc00000) for both.
+ * The percentiles are checked before the no-op. */
+int ksmi_scene_quantile_select(const uint64_t* sorted_u64, int64_t HW, int64_t N, const int32_t* percentiles_host_i32, int P, int32_t* valid_i32,
+                               float* lower_f32, float* higher_f32, void* stream);
+/* ksmi_scene_quantile_segments: the reference has no counterpart.  offsets_i32 [N + 1]: offsets_i32[r] = the lower bound of r << 32
+ * in sorted_u64 [HW], so row r holds sorted_f32[offsets_i32[r] .. offsets_i32[r + 1]) and offsets_i32[N] pixels take part in all;
+ * sorted_f32 [HW]: the value field of every composite turned back into float bits (past offsets_i32[N]: the field of all ones, not a
+ * value of the raster). */
+int ksmi_scene_quantile_segments(const uint64_t* sorted_u64, int64_t HW, int64_t N, int32_t* offsets_i32, float* sorted_f32, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -217,6 +217,13 @@ SIGNATURES = {
     "ksmi_scene_zonal_mark": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "ksmi_scene_zonal_tables": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ksmi_scene_zonal_accumulate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ksmi_scene_quantile_passes": (_i, [_i64]),
+    "ksmi_scene_quantile_scratch": (_i64, [_i64]),
+    "ksmi_scene_quantile_zones": (_i, [_vp, _vp, _i64, _i64, _vp, _vp]),
+    "ksmi_scene_quantile_keys": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "ksmi_scene_quantile_sort": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "ksmi_scene_quantile_select": (_i, [_vp, _i64, _i64, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp]),
+    "ksmi_scene_quantile_segments": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
     "ksmi_bmm_f32":(_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
     "ksmi_softmax_rows_f32": (_i, [_vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_softmax_rows_backward_f32": (_i, [_vp, _vp, _vp, _i64, _i, C.c_float, _vp]),

@@ -17,9 +17,13 @@ pass and a row pass, integers throughout, equal to tests/depth_ref.py) and one s
 rasters per zone of a zone raster -- pixel count, bounding box, coordinate sums and per band the finite count, the extremes under a
 total order and a fixed-point sum; integers and min / max only, equal to tests/zonal_ref.py -- and `component_stats` keys it by the
 component labels, so that the depth and the scores meet the polygons: `polygons_geojson(..., attributes=)` joins the rows to the
-features by label.  Everything runs on the current stream; nothing synchronises but the three counts (edges, rings, vertices) that
-`polygonize` reads to size its buffers and the one count (zones) that `zonal_stats` reads to size its tables."""
+features by label.  `zonal_quantiles` (csrc/quantile.hip) sorts a band's finite values per zone -- 64-bit composites of row and value
+key through a stable radix sort, equal to tests/quantile_ref.py -- and selects percentiles on the sorted order; `zonal_sorted` hands
+out the sorted segments themselves and `component_quantiles` keys the percentiles by the component labels.  Everything runs on the
+current stream; nothing synchronises but the three counts (edges, rings, vertices) that `polygonize` reads to size its buffers and
+the one count (zones) that `zonal_stats` and `zonal_quantiles` read to size their tables."""
 import gc
+import math
 from collections import namedtuple
 
 import numpy as np
@@ -40,6 +44,10 @@ Rings = namedtuple("Rings", "label ring_id start area2 verts")
 MAX_ZONAL_BANDS = 8               # ZN_MAX_B of csrc/zonal.hip
 ZONAL_BLOCK = (4096, 64)          # (ZN_PER_BLOCK, ZN_SLOTS) of csrc/zonal.hip: the pixels of a workgroup, the zones it combines in LDS
 Zonal = namedtuple("Zonal", "zone count bbox sum_x sum_y valid vmin vmax vsum frac_bits")
+MAX_PERCENTILES = 16              # QT_MAX_P of csrc/quantile.hip
+QUANTILE_TILE = 4096              # QT_TILE of csrc/quantile.hip: the composites one workgroup counts and scatters in a radix pass
+ZonalQuantiles = namedtuple("ZonalQuantiles", "zone valid lower higher percentiles")
+QUANTILE_METHODS = ("linear", "lower", "higher", "midpoint", "nearest")
 SCORES = {None: None, "logits": 0, "softmax": 1}
 # test-time view sets, in ascending code; a code's bit 2 transposes the window (first), bit 1 then flips y, bit 0 then flips x
 VIEW_SETS = {"hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -674,6 +682,19 @@ def _check_zonal(zones, values, where, frac_bits, name):
     return values
 
 
+def _zonal_rows(zones, where):
+    """the presence flags of the zones, their exclusive scan (the row of every present zone) and N, the one value read on the host ->
+    (present int32 [HW], row int32 [HW], N); (None, None, 0) for an empty scene"""
+    HW = zones.numel()
+    if not HW:
+        return None, None, 0
+    present = torch.empty(HW, dtype=torch.int32, device=zones.device)
+    _lib.check(_lib.load().ksmi_scene_zonal_mark(zones.data_ptr(), None if where is None else where.data_ptr(), HW, present.data_ptr(),
+                                                 stream_ptr()), "scene_zonal_mark")
+    row = torch.empty(HW, dtype=torch.int32, device=zones.device)
+    return present, row, int(_scan(present, row, "scan_i32").item())    # the one host read
+
+
 def zonal_stats(zones, values=None, where=None, frac_bits=16):
     """Statistics of value rasters per zone of a zone raster -> Zonal, device tensors.
 
@@ -701,14 +722,8 @@ def zonal_stats(zones, values=None, where=None, frac_bits=16):
     dev, HW = zones.device, zones.numel()
     Hs, Ws = zones.shape
     B = 0 if values is None else values.shape[0]
-    N = 0
     lib, st = _lib.load(), stream_ptr()
-    if HW:
-        present = torch.empty(HW, dtype=torch.int32, device=dev)
-        _lib.check(lib.ksmi_scene_zonal_mark(zones.data_ptr(), None if where is None else where.data_ptr(), HW, present.data_ptr(), st),
-                   "scene_zonal_mark")
-        row = torch.empty(HW, dtype=torch.int32, device=dev)
-        N = int(_scan(present, row, "scan_i32").item())                 # the one host read
+    present, row, N = _zonal_rows(zones, where)
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
     i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=dev)
     f32 = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
@@ -738,6 +753,167 @@ def component_stats(classes, select=(1, 2), values=None, labels=None, frac_bits=
     if labels is None:
         labels = label_components(classes, 4)
     return zonal_stats(labels, values, select_classes(classes, select), frac_bits)
+
+
+# ---------------------------------------------------------------------------------------------------- percentiles per zone
+def basis_points(percentiles, name="zonal_quantiles"):
+    """percents (one number or a sequence: 50, 97.5, 99.99) -> the tuple of basis points c = round(100 * p), in the order given.  A p
+    that is no finite real number, that is further than 1e-9 from c / 100, or whose c is outside 0 .. 10000 is refused, and so are an
+    empty sequence and more than MAX_PERCENTILES."""
+    if isinstance(percentiles, (int, float, np.integer, np.floating)):
+        percentiles = (percentiles,)
+    try:
+        given = tuple(percentiles)
+    except TypeError:
+        raise ValueError(f"{name}: percentiles is a sequence of percents, got {percentiles!r}") from None
+    if not 1 <= len(given) <= MAX_PERCENTILES:
+        raise ValueError(f"{name}: 1 .. {MAX_PERCENTILES} percentiles, got {len(given)}")
+    out = []
+    for p in given:
+        if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, float, np.integer, np.floating)) or not math.isfinite(p):
+            raise ValueError(f"{name}: a percentile is a percent 0 .. 100, got {p!r}")
+        c = int(round(100 * float(p)))
+        if abs(float(p) - c / 100) > 1e-9:
+            raise ValueError(f"{name}: a percentile is a whole number of basis points (hundredths of a percent), got {p!r}")
+        if not 0 <= c <= 10000:
+            raise ValueError(f"{name}: a percentile is a percent 0 .. 100, got {p!r}")
+        out.append(c)
+    return tuple(out)
+
+
+def percentile_name(c):
+    """the name of the basis point c: "p" and the percent with trailing zeros stripped and "." written as "_": p50, p97_5, p0_01"""
+    c = int(c)
+    if not 0 <= c <= 10000:
+        raise ValueError(f"percentile_name: a basis point 0 .. 10000, got {c}")
+    whole, part = divmod(c, 100)
+    return f"p{whole}" + (("_" + f"{part:02d}".rstrip("0")) if part else "")
+
+
+def quantile_values(zq, method="linear"):
+    """The percentiles of a ZonalQuantiles as float64 [B, P, N], combined on the host from its `lower` and `higher` in float64.  With
+    g = c * (valid - 1) % 10000 (the position's fraction in basis points): "linear" lower + (higher - lower) * (g / 10000); "lower";
+    "higher"; "midpoint" (lower + higher) / 2; "nearest" lower if 2 * g <= 10000 else higher.  NaN where valid == 0."""
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f"quantile_values: method is one of {', '.join(QUANTILE_METHODS)}, got {method!r}")
+    host = lambda t: t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    lower, higher, valid = host(zq.lower).astype(np.float64), host(zq.higher).astype(np.float64), host(zq.valid).astype(np.int64)
+    c = np.asarray(zq.percentiles, np.int64).reshape(1, -1, 1)
+    g = c * np.maximum(valid[:, None, :] - 1, 0) % 10000
+    if method == "lower":
+        return lower
+    if method == "higher":
+        return higher
+    if method == "midpoint":
+        return (lower + higher) / 2.0
+    if method == "nearest":
+        return np.where(2 * g <= 10000, lower, higher)
+    return lower + (higher - lower) * (g / 10000.0)
+
+
+def _sorted_composites(zones, band_ptr, where, row, N):
+    """the composites of one band (a device address of HW float32), sorted -> int64 [HW] holding them as unsigned 64-bit integers"""
+    HW, dev = zones.numel(), zones.device
+    lib, st = _lib.load(), stream_ptr()
+    keys, alt = torch.empty(HW, dtype=torch.int64, device=dev), torch.empty(HW, dtype=torch.int64, device=dev)
+    need = int(lib.ksmi_scene_quantile_scratch(HW))
+    scratch = torch.empty(need, dtype=torch.int32, device=dev)
+    _lib.check(lib.ksmi_scene_quantile_keys(zones.data_ptr(), None if where is None else where.data_ptr(), band_ptr, row.data_ptr(), HW, N,
+                                            keys.data_ptr(), st), "scene_quantile_keys")
+    _lib.check(lib.ksmi_scene_quantile_sort(keys.data_ptr(), alt.data_ptr(), HW, N, scratch.data_ptr(), need, st), "scene_quantile_sort")
+    return keys if int(lib.ksmi_scene_quantile_passes(N)) % 2 == 0 else alt          # an odd number of passes ends in the other buffer
+
+
+def zonal_quantiles(zones, values, percentiles=(50,), where=None):
+    """Percentiles of value rasters per zone of a zone raster -> ZonalQuantiles(zone, valid, lower, higher, percentiles).
+
+    zones, where, the skip rule and the rows are those of zonal_stats.  values: float32 [B, Hs, Ws] or [Hs, Ws], 1 <= B <= 8.
+    percentiles: 1 .. 16 percents such as 50, 97.5 or 99.99, whole numbers of basis points (basis_points).  For band b and row r, s is
+    the ascending sequence of the finite values of the row's pixels, ordered by the key bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000)
+    compared unsigned (-0.0 < +0.0), and n its length:
+      zone        int32 [N]         the zone id
+      valid       int32 [B, N]      n: zonal_stats(...).valid
+      lower       float32 [B, P, N] s[k]            with pos = c * (n - 1) in integers, k = pos // 10000, g = pos % 10000: what
+      higher      float32 [B, P, N] s[k + (g > 0)]  np.percentile(method="lower") and "higher" give, the position taken exactly;
+                                                    NaN where n == 0.  Bit copies of input values.
+      percentiles tuple [P]         the basis points c, in the order given
+    quantile_values combines lower and higher on the host ("linear" by default).  Equal keys are equal bits, so the sorted sequence is
+    unique: the bits are those of tests/quantile_ref.py on every run.  Launches: the presence flags and their scan (as zonal_stats),
+    the zone ids, and per band the composites (row << 32 | key; all ones where a pixel takes no part), a stable radix sort of 8-bit
+    digits over all Hs * Ws composites (4 value passes and one per started byte of N - 1: 4 .. 8 passes of three launches) and the
+    selection (two binary searches per row, shared by its percentiles).  One integer, N, is read on the host, as in zonal_stats, and nothing
+    else.  Scratch: 8 B per pixel (the flags and their scan), 16 B per pixel (two buffers of composites) and 1 KiB of counters per
+    4096 pixels: 24.25 B per pixel, 487 MB for a scene of 4480 x 4480.  Bands go one at a time, so scratch does not grow with B.  The
+    inputs are left unchanged.  No zone present, or an empty scene: empty tensors."""
+    name = "zonal_quantiles"
+    values = _check_zonal(zones, values, where, 16, name)
+    if values is None or values.shape[0] < 1:
+        raise ValueError(f"{name}: values is a contiguous float32 tensor [B, Hs, Ws] or [Hs, Ws] on the map's device, 1 <= B <= {MAX_ZONAL_BANDS}")
+    pcts = basis_points(percentiles, name)
+    require_gpu(zones)
+    dev, HW, B, P = zones.device, zones.numel(), values.shape[0], len(pcts)
+    lib, st = _lib.load(), stream_ptr()
+    present, row, N = _zonal_rows(zones, where)
+    out = ZonalQuantiles(torch.empty(N, dtype=torch.int32, device=dev), torch.empty((B, N), dtype=torch.int32, device=dev),
+                         torch.empty((B, P, N), dtype=torch.float32, device=dev), torch.empty((B, P, N), dtype=torch.float32, device=dev), pcts)
+    if N:
+        _lib.check(lib.ksmi_scene_quantile_zones(present.data_ptr(), row.data_ptr(), HW, N, out.zone.data_ptr(), st), "scene_quantile_zones")
+        del present
+        host_pcts = (_lib.C.c_int32 * P)(*pcts)
+        for b in range(B):
+            ordered = _sorted_composites(zones, values[b].data_ptr(), where, row, N)
+            _lib.check(lib.ksmi_scene_quantile_select(ordered.data_ptr(), HW, N, host_pcts, P, out.valid[b].data_ptr(), out.lower[b].data_ptr(),
+                                                      out.higher[b].data_ptr(), st), "scene_quantile_select")
+            del ordered
+    return out
+
+
+def zonal_sorted(zones, values2d, where=None):
+    """The sorted values of one band per zone -> (zone int32 [N], offsets int32 [N + 1], sorted float32 [Hs * Ws]), device tensors: the
+    primitive under zonal_quantiles.  values2d: float32 [Hs, Ws].  sorted[offsets[r]:offsets[r + 1]] holds the finite values of the
+    pixels of row r in ascending key order (zonal_quantiles), offsets[0] == 0 and offsets[N] is the number of pixels that take part;
+    what lies past offsets[N] is unspecified.  The launches, the one host read (N) and the scratch are those of zonal_quantiles for
+    one band.  No zone present, or an empty scene: zone is empty, offsets == [0] and sorted has Hs * Ws unspecified elements."""
+    name = "zonal_sorted"
+    if torch.is_tensor(values2d) and values2d.dim() != 2:
+        raise ValueError(f"{name}: values2d is a contiguous float32 tensor [Hs, Ws] on the map's device")
+    values = _check_zonal(zones, values2d, where, 16, name)
+    if values is None:
+        raise ValueError(f"{name}: values2d is a contiguous float32 tensor [Hs, Ws] on the map's device")
+    require_gpu(zones)
+    dev, HW = zones.device, zones.numel()
+    lib, st = _lib.load(), stream_ptr()
+    present, row, N = _zonal_rows(zones, where)
+    zone = torch.empty(N, dtype=torch.int32, device=dev)
+    offsets = torch.zeros(N + 1, dtype=torch.int32, device=dev)
+    ordered = torch.empty(HW, dtype=torch.float32, device=dev)
+    if N:
+        _lib.check(lib.ksmi_scene_quantile_zones(present.data_ptr(), row.data_ptr(), HW, N, zone.data_ptr(), st), "scene_quantile_zones")
+        del present
+        composites = _sorted_composites(zones, values.data_ptr(), where, row, N)
+        _lib.check(lib.ksmi_scene_quantile_segments(composites.data_ptr(), HW, N, offsets.data_ptr(), ordered.data_ptr(), st),
+                   "scene_quantile_segments")
+    return zone, offsets, ordered
+
+
+def component_quantiles(classes, values, percentiles=(50,), select=(1, 2), labels=None):
+    """zonal_quantiles over the 4-connected components of the classes in `select` -> ZonalQuantiles: zones = labels
+    (label_components(classes, 4) unless given), where = select_classes(classes, select), as component_stats keys zonal_stats.  Its
+    rows are those of component_stats(classes, select) and the features of polygonize(classes, select), in the same order."""
+    name = "component_quantiles"
+    _select_mask(select, name)
+    if not torch.is_tensor(classes) or classes.dtype != torch.uint8 or classes.dim() != 2 or not classes.is_contiguous():
+        raise ValueError(f"{name}: classes is a contiguous uint8 device tensor [Hs, Ws]")
+    if labels is not None and (not torch.is_tensor(labels) or labels.shape != classes.shape or labels.device != classes.device):
+        raise ValueError(f"{name}: labels has the shape and the device of classes")
+    checked = _check_zonal_values(values, classes, 16, name)
+    if checked is None or checked.shape[0] < 1:
+        raise ValueError(f"{name}: values is a contiguous float32 tensor [B, Hs, Ws] or [Hs, Ws] on the map's device, 1 <= B <= {MAX_ZONAL_BANDS}")
+    basis_points(percentiles, name)
+    require_gpu(classes)
+    if labels is None:
+        labels = label_components(classes, 4)
+    return zonal_quantiles(labels, values, percentiles, select_classes(classes, select))
 
 
 # ---------------------------------------------------------------------------------------------------- the scene loop

@@ -7,7 +7,7 @@
       [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] [--tta hflip] \\
       [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
       [--polygons flood.geojson --polygon_classes 1 2] [--components components.csv] \\
-      [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2]]
+      [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2] [--percentiles 50 90]]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
 nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
@@ -63,8 +63,19 @@ and NaN become NaN, no gap is filled and nothing is standardised (the model's co
 float32 Deflate GeoTIFF in tiles of 256 with nodata NaN and the first post file's georeferencing: 0 on dry land, NaN at invalid
 pixels, at water without a DEM value and where the scene has no shore at all.  --report then gains a key "depth": "water_pixels",
 "with_depth" (those with a finite depth), "max" and "mean" over them, and "volume" (their sum in float64 times "pixel_area"; null
-without georeferencing).  FwDET's smoothing filter, cost-distance allocation, medians and percentiles per component and a DEM on
-another grid are outside this tool."""
+without georeferencing).  FwDET's smoothing filter, cost-distance allocation and a DEM on another grid are outside this tool.
+
+--percentiles P [P ...] (percents, whole numbers of basis points, each once: 50 90 97.5) adds percentiles of the depth, which a few pixels that
+took their level from another water body's shore hardly move, where they move the mean and the maximum a lot.  It needs --depth_out
+and one of --components, --polygons, --report.  The depth raster still on the device is sorted per component on the device
+(kurosiwo_amd.scene.component_quantiles, zonal_quantiles: a segmented radix sort and a selection; the same bits on every run) and
+nothing is read back but the tables.  Every row of --components and every feature of --polygons gains one column or property per
+percentile after "volume": "depth_p" and the percent with trailing zeros stripped and "." written as "_" (depth_p50, depth_p97_5),
+the percentile over the component's pixels with a finite depth, interpolated linearly between the two neighbouring sorted values in
+float64 as np.percentile does (the position c * (n - 1) / 10000 taken in exact integers); null for a component without such a
+pixel.  The "depth" key of --report gains "percentiles": {"p50": ..., "p90": ...} over all pixels of --depth_classes with a finite
+depth (one zone: the whole water surface); null values without such a pixel.  Percentiles of the confidence, weighted percentiles
+and zones from a vector layer are outside this tool."""
 import argparse
 import json
 import os
@@ -81,8 +92,9 @@ if ROOT not in sys.path:
 from kurosiwo_amd import geotiff                                            # noqa: E402
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
-from kurosiwo_amd.scene import (cd_forward, component_stats, flood_depth, label_components, polygonize, polygons_geojson, predict_scene,      # noqa: E402
-                                seg_forward, sieve, zonal_geometry)
+from kurosiwo_amd.scene import (basis_points, cd_forward, component_quantiles, component_stats, flood_depth, label_components,      # noqa: E402
+                                percentile_name, polygonize, polygons_geojson, predict_scene, quantile_values, seg_forward, select_classes,
+                                sieve, zonal_geometry, zonal_quantiles)
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -119,6 +131,8 @@ parser.add_argument("--components", default=None, help="FILE.csv: one row of sta
 parser.add_argument("--depth_out", default=None, help="FILE.tif: the water depth of the map as written, in the DEM's unit")
 parser.add_argument("--depth_dem", default=None, help="the DEM the depth is taken from, raw, on the scene's grid (default: the file of --dem)")
 parser.add_argument("--depth_classes", type=int, nargs="+", default=[1, 2])
+parser.add_argument("--percentiles", type=float, nargs="+", default=None,
+                    help="percents (50 90 97.5): percentiles of the depth per component and over all water; needs --depth_out and a table")
 
 
 def read_date(paths, nodata):
@@ -164,10 +178,22 @@ DEPTH_COLUMNS = ("depth_pixels", "depth_max", "depth_mean", "volume")
 DEPTH_FRAC_BITS, SCORE_FRAC_BITS = 16, 30
 
 
-def component_table(classes, written, select, depth, score, area, pixel_scale, origin):
+def percentile_columns(pcts):
+    """the column names of the basis points pcts: depth_p50, depth_p97_5"""
+    return tuple("depth_" + percentile_name(c) for c in pcts)
+
+
+def percentile_cells(zq):
+    """the "linear" percentiles of band 0 of a ZonalQuantiles -> one list per percentile, one value per row; None without a finite value"""
+    some = (zq.valid[0] > 0).cpu().numpy().tolist()
+    return [[v if ok else None for v, ok in zip(column, some)] for column in quantile_values(zq, "linear")[0].tolist()]
+
+
+def component_table(classes, written, select, depth, score, area, pixel_scale, origin, percents=None):
     """the statistics of the components of the classes `select` of the device map `classes` (`written`: its host copy) -> (Zonal,
     {column: one value per row}): the columns of --components after "label", in order; depth (device float32 [Hs, Ws] or None) adds
-    DEPTH_COLUMNS, score (device softmax [K, Hs, Ws] or None) adds "confidence".  None is a null."""
+    DEPTH_COLUMNS and, with `percents`, one column per percentile; score (device softmax [K, Hs, Ws] or None) adds "confidence".
+    None is a null."""
     labels = label_components(classes, 4)
     geom = deep = component_stats(classes, select, values=depth, labels=labels, frac_bits=DEPTH_FRAC_BITS)
     zone, count, box = geom.zone.cpu().numpy(), geom.count.cpu().numpy(), geom.bbox.cpu().numpy()
@@ -182,6 +208,10 @@ def component_table(classes, written, select, depth, score, area, pixel_scale, o
         cols["depth_max"] = [float(v) if k else None for v, k in zip(top.tolist(), n.tolist())]
         cols["depth_mean"] = [m / k if k else None for m, k in zip(metres.tolist(), n.tolist())]
         cols["volume"] = [None if area is None else m * area for m in metres.tolist()]
+        if percents:
+            zq = component_quantiles(classes, depth, percents, select, labels=labels)
+            assert torch.equal(zq.zone, geom.zone) and torch.equal(zq.valid, deep.valid)
+            cols.update(zip(percentile_columns(zq.percentiles), percentile_cells(zq)))
     if score is not None:
         conf = component_stats(classes, select, values=score, labels=labels, frac_bits=SCORE_FRAC_BITS)
         n, total = conf.valid.cpu().numpy(), conf.vsum.cpu().numpy()
@@ -230,6 +260,16 @@ def main(argv=None):
     depth_dem = args.depth_dem or args.dem
     if args.depth_out is not None and depth_dem is None:
         raise SystemExit("predict.py: --depth_out needs a DEM: pass --depth_dem (or --dem)")
+    pcts = ()
+    if args.percentiles is not None:
+        if args.depth_out is None or (args.components is None and args.polygons is None and args.report is None):
+            raise SystemExit("predict.py: --percentiles needs --depth_out and one of --components, --polygons, --report")
+        try:
+            pcts = basis_points(args.percentiles, "predict.py: --percentiles")
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        if len(set(pcts)) != len(pcts):
+            raise SystemExit("predict.py: --percentiles names a percentile twice")
     method = args.method.lower()
     task = args.task or ("cd" if method in CD_METHODS else "segmentation")
     dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
@@ -307,13 +347,18 @@ def main(argv=None):
         depth_report = {"water_pixels": int(np.isin(written, args.depth_classes).sum()), "with_depth": int(deep.size),
                         "max": float(deep.max()) if deep.size else None, "mean": float(deep.mean()) if deep.size else None,
                         "volume": None if area is None else float(deep.sum()) * area}
+        if pcts and args.report is not None:            # one zone: the whole water surface, from the tensor still on the device
+            surface = zonal_quantiles(torch.zeros_like(classes, dtype=torch.int32), depth_dev, args.percentiles,
+                                      select_classes(classes, args.depth_classes))
+            cells = percentile_cells(surface) if surface.zone.numel() else [[None]] * len(pcts)
+            depth_report["percentiles"] = {percentile_name(c): cell[0] for c, cell in zip(pcts, cells)}
         print(f"wrote {args.depth_out}: depth at {depth_report['with_depth']} of {depth_report['water_pixels']} pixels of classes "
               f"{' '.join(str(c) for c in args.depth_classes)}" + (f", at most {depth_report['max']:.3f}" if deep.size else ""))
     zonal = cols = None
     if args.polygons is not None or args.components is not None:        # the statistics stay on the device until the tables are read
         zonal, cols = component_table(classes, written, args.polygon_classes, depth_dev, score if args.score == "softmax" else None, area,
-                                      geo["pixel_scale"], geo["origin"])
-        assert tuple(["label"] + list(cols)) == COMPONENT_COLUMNS + (DEPTH_COLUMNS if depth_dev is not None else ()) + (
+                                      geo["pixel_scale"], geo["origin"], args.percentiles if pcts else None)
+        assert tuple(["label"] + list(cols)) == COMPONENT_COLUMNS + (DEPTH_COLUMNS + percentile_columns(pcts) if depth_dev is not None else ()) + (
             ("confidence",) if args.score == "softmax" else ())
     if args.components is not None:
         write_components(args.components, zonal, cols)
@@ -333,7 +378,7 @@ def main(argv=None):
         print(f"wrote {args.report}")
     if args.polygons is not None:
         rings = polygonize(classes, select=args.polygon_classes)
-        extra = {k: v for k, v in cols.items() if k in DEPTH_COLUMNS or k == "confidence"}
+        extra = {k: v for k, v in cols.items() if k in DEPTH_COLUMNS + percentile_columns(pcts) or k == "confidence"}
         collection = polygons_geojson(rings, written, pixel_scale=geo["pixel_scale"], origin=geo["origin"],
                                       attributes=(zonal, extra) if extra else None)
         with open(args.polygons, "w") as f:

@@ -1,7 +1,7 @@
 """Where a whole-scene pass spends its time (kurosiwo_amd/scene.py: predict_scene; the numbers behind profiles/scene_probe.txt).
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
-                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth] [--zonal]
+                                [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth] [--zonal] [--quantiles]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -46,6 +46,18 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              (ksmi_scene_zonal_mark), scan (ksmi_scan_i32), tables (ksmi_scene_zonal_tables), accumulate (ksmi_scene_zonal_accumulate:
              keys, the pass, keys back), and their sum; the labels they start from are timed apart.  Next to them, in the same call
              on the same maps, the event time of flood_depth and of polygonize end to end.
+  quantiles  with --quantiles (the numbers behind profiles/quantile_probe.txt), instead of the passes above:
+             kurosiwo_amd.scene.zonal_quantiles with three percentiles (50, 90, 99) of one value band keyed by the 4-connectivity labels
+             of a size x size class map, `where` = its classes 1 and 2, of five contents -- the four of --zonal and "sparse": the lake
+             with a `where` that keeps one lake pixel in sixteen, about 2 % of the scene.  The value raster is flood_depth of the map
+             over the smooth DEM of --depth; a map without a shore (one class everywhere) has no depth, and the DEM itself stands in.
+             Per map: the event time of zonal_quantiles end to end, the number of radix passes, and the event time of each stage of
+             the same sequence: rows (ksmi_scene_zonal_mark, ksmi_scan_i32 and the read of N, ksmi_scene_quantile_zones), keys
+             (ksmi_scene_quantile_keys), sort (ksmi_scene_quantile_sort), select (ksmi_scene_quantile_select).  The yardstick, in the
+             same process and alternated with it repeat by repeat, is the library route the project would otherwise call, written
+             with torch ops only: the presence flags by index_fill_, their cumsum and the read of N, int64 composites, torch.sort,
+             torch.searchsorted for the segment bounds and a gather; its valid, lower and higher are checked equal to
+             zonal_quantiles' bit for bit.
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -75,6 +87,7 @@ def main():
     ap.add_argument("--geojson_max_rings", type=int, default=2_000_000)
     ap.add_argument("--depth", action="store_true", default=False)
     ap.add_argument("--zonal", action="store_true", default=False)
+    ap.add_argument("--quantiles", action="store_true", default=False)
     ap.add_argument("--tta", nargs="+",choices=("none", "hflip", "flips", "d4"), default=None)
     a = ap.parse_args()
     import numpy as np
@@ -105,6 +118,9 @@ def main():
         return finish()
     if a.zonal:
         zonal_probe(a, emit, ev, med)
+        return finish()
+    if a.quantiles:
+        quantile_probe(a, emit, ev, med)
         return finish()
     if a.mmu is not None:
         sieve_probe(a, emit, ev, med)
@@ -497,6 +513,124 @@ def zonal_probe(a, emit, ev, med):
         polygon_ms = med(timed(lambda: scene.polygonize(d, (1, 2), labels=labels))[0] for _ in range(min(a.repeats, 3) + 1))
         emit(what="zonal_beside", content=name, size=S, flood_depth_ms=round(depth_ms, 3), polygonize_ms=round(polygon_ms, 3))
         del d, labels, where
+
+
+def quantile_probe(a, emit, ev, med):
+    """zonal_quantiles on five maps of a.size x a.size, timed whole and per stage, against torch.sort on the same composites"""
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib, scene
+    from kurosiwo_amd.runtime import stream_ptr
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    S, lib, st = a.size, _lib.load(), stream_ptr()
+    HW = S * S
+    percents = (50, 90, 99)
+    pcts = scene.basis_points(percents)
+    P = len(pcts)
+    yy, xx = np.mgrid[0:S, 0:S]
+    radius = 1500 * S // 4480
+    lake = ((yy - S // 2) ** 2 + (xx - S // 2) ** 2 <= radius * radius).astype(np.uint8)
+    maps = {"one_class": np.ones((S, S), np.uint8), "speckle": sieve_ref.speckle_scene(4480, S, S), "lake": lake,
+            "checkerboard": ((yy + xx) & 1).astype(np.uint8), "sparse": lake}
+    dem = torch.from_numpy((100.0 + 20.0 * np.sin(yy / 97.0) * np.cos(xx / 131.0)).astype(np.float32)).cuda()
+    del yy, xx, lake
+    g = torch.Generator(device="cpu").manual_seed(4480)
+    thin = (torch.rand((S, S), generator=g) < 1.0 / 16.0).to(torch.uint8).cuda()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    chk = _lib.check
+    scan_need, sort_need = int(lib.ksmi_scan_i32_scratch(HW)), int(lib.ksmi_scene_quantile_scratch(HW))
+    host_pcts = (_lib.C.c_int32 * P)(*pcts)
+    stages = ("rows", "keys", "sort", "select")
+    bits = lambda t: t.view(torch.int32)
+
+    def timed(fn):
+        e0, e1 = ev(), ev()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def staged(labels, where, v):
+        present, row = (torch.empty(HW, dtype=torch.int32, device="cuda") for _ in range(2))
+        total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        scratch = torch.empty(max(scan_need, 1), dtype=torch.int32, device="cuda")
+        keys, alt = (torch.empty(HW, dtype=torch.int64, device="cuda") for _ in range(2))
+        counters = torch.empty(sort_need, dtype=torch.int32, device="cuda")
+        e = [ev() for _ in range(5)]
+        e[0].record()
+        chk(lib.ksmi_scene_zonal_mark(ptr(labels), ptr(where), HW, ptr(present), st), "scene_zonal_mark")
+        chk(lib.ksmi_scan_i32(ptr(present), ptr(row), HW, ptr(total), ptr(scratch), scan_need, st), "scan_i32")
+        N = int(total.item())                                                  # the one host read
+        zone, valid = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty((1, N), dtype=torch.int32, device="cuda")
+        lower, higher = (torch.empty((1, P, N), dtype=torch.float32, device="cuda") for _ in range(2))
+        chk(lib.ksmi_scene_quantile_zones(ptr(present), ptr(row), HW, N, ptr(zone), st), "scene_quantile_zones")
+        e[1].record()
+        chk(lib.ksmi_scene_quantile_keys(ptr(labels), ptr(where), ptr(v), ptr(row), HW, N, ptr(keys), st), "scene_quantile_keys")
+        e[2].record()
+        chk(lib.ksmi_scene_quantile_sort(ptr(keys), ptr(alt), HW, N, ptr(counters), sort_need, st), "scene_quantile_sort")
+        e[3].record()
+        ordered = keys if lib.ksmi_scene_quantile_passes(N) % 2 == 0 else alt
+        chk(lib.ksmi_scene_quantile_select(ptr(ordered), HW, N, host_pcts, P, ptr(valid), ptr(lower), ptr(higher), st), "scene_quantile_select")
+        e[4].record()
+        torch.cuda.synchronize()
+        return [e[j].elapsed_time(e[j + 1]) for j in range(4)], scene.ZonalQuantiles(zone, valid, lower, higher, pcts)
+
+    def library_route(labels, where, v):
+        """the same table through torch ops: flags, cumsum, int64 composites, torch.sort, searchsorted, gather"""
+        z = labels.view(-1).long()
+        w = v.view(-1)
+        live = (z >= 0) & (z < HW) & (where.view(-1) != 0)
+        present = torch.zeros(HW, dtype=torch.int64, device="cuda").index_fill_(0, z[live], 1)
+        row = torch.cumsum(present, 0) - present
+        N = int(present.sum().item())                                          # the same one host read
+        part = live & torch.isfinite(w)
+        b = bits(w).long() & 0xFFFFFFFF
+        key = b ^ torch.where(b >> 31 != 0, 0xFFFFFFFF, 0x80000000)
+        comp = torch.where(part, (row[z.clamp(0, HW - 1)] << 32) | key, torch.iinfo(torch.int64).max)
+        ordered = torch.sort(comp).values
+        bounds = torch.searchsorted(ordered, torch.arange(N + 1, dtype=torch.int64, device="cuda") << 32)
+        n = bounds[1:] - bounds[:-1]
+        c = torch.tensor(pcts, dtype=torch.int64, device="cuda")[:, None]
+        pos = c * (n - 1).clamp(min=0)[None, :]
+        k, frac = pos // 10000, pos % 10000
+        top = HW - 1
+        unkey = lambda q: (q ^ torch.where(q >> 31 != 0, 0x80000000, 0xFFFFFFFF)).to(torch.int32)      # wraps to the float's bits
+        pick = lambda i: torch.where(n[None, :] > 0, unkey(ordered[(bounds[:-1][None, :] + i).clamp(max=top)] & 0xFFFFFFFF), 0x7FC00000)
+        return n.to(torch.int32), pick(k), pick(k + (frac > 0))
+
+    for name, m in maps.items():
+        d = torch.from_numpy(m).cuda()
+        labels, where = scene.label_components(d, 4), scene.select_classes(d, (1, 2))
+        if name == "sparse":
+            where = where * thin
+        v = scene.flood_depth(d, dem)
+        if not bool(torch.isfinite(v).any()):                                  # no shore: the DEM stands in for the depth
+            v = dem
+        _, first = staged(labels, where, v)                                    # warm-up
+        whole = scene.zonal_quantiles(labels, v, percents, where)
+        same = lambda p, q: all(torch.equal(bits(x) if x.dtype == torch.float32 else x, bits(y) if y.dtype == torch.float32 else y)
+                                for x, y in zip(p[:-1], q[:-1]))
+        assert same(first, whole)                                              # the staged sequence is zonal_quantiles
+        n, lo, hi = library_route(labels, where, v)                            # warm-up, and the check
+        assert torch.equal(n, whole.valid[0]) and torch.equal(lo.to(torch.int32), bits(whole.lower[0])) and torch.equal(
+            hi.to(torch.int32), bits(whole.higher[0]))
+        del n, lo, hi
+        ours, theirs, split = [], [], []
+        for _ in range(a.repeats):                                             # alternated
+            ours.append(timed(lambda: scene.zonal_quantiles(labels, v, percents, where))[0])
+            theirs.append(timed(lambda: library_route(labels, where, v))[0])
+            t, again = staged(labels, where, v)
+            split.append(t)
+        assert same(first, again)                                              # equal bits
+        t = [med(r[j] for r in split) for j in range(4)]
+        N = int(first.zone.numel())
+        emit(what="quantiles", content=name, size=S, percentiles=P, zones=N, taking_part=int(whole.valid.sum()),
+             kept_by_where=round(float(where.count_nonzero()) / HW, 4), radix_passes=int(lib.ksmi_scene_quantile_passes(N)),
+             zonal_quantiles_ms=round(med(ours), 3), torch_sort_route_ms=round(med(theirs), 3), ratio=round(med(ours) / med(theirs), 3),
+             **{k + "_ms": round(x, 3) for k, x in zip(stages, t)}, staged_total_ms=round(sum(t), 3))
+        del d, labels, where, v, first, whole, again
 
 
 def sieve_probe(a, emit, ev, med):
