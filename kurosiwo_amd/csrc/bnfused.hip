@@ -8,7 +8,7 @@
 // bits), computes the per-channel constants into LDS, and then streams.  Workgroup 0 publishes what later launches read (saved
 // mean / rstd / scale / shift, running statistics, dgamma / dbeta).  The arithmetic of the streaming part is the expression of the
 // kernel it replaces, so the two paths agree bit for bit whenever the fp64 row sums round to the same float (tests:
-// tests/test_gpu_kernels.py::test_bn_fused_*).
+// tests/test_gpu_bnfused.py, every launcher against the float64 oracles of tests/bnfused_ref.py and against that sequence).
 //
 //   ksmi_bn_fin_add_relu           = ksmi_bn_finalize + ksmi_bn_add_relu (+ ksmi_maxpool2x2_forward)
 //   ksmi_bn_bwd_fin_apply_gated    = ksmi_reduce_rows + ksmi_bn_bwd_apply_gated
