@@ -984,6 +984,38 @@ int ksmi_scene_quantile_select(const uint64_t* sorted_u64, int64_t HW, int64_t N
  * sorted_f32 [HW]: the value field of every composite turned back into float bits (past offsets_i32[N]: the field of all ones, not a
  * value of the raster). */
 int ksmi_scene_quantile_segments(const uint64_t* sorted_u64, int64_t HW, int64_t N, int32_t* offsets_i32, float* sorted_f32, void* stream);
+/* Zones from a vector layer (csrc/zones.hip; kurosiwo_amd/scene.py: rasterize_zones; predict.py --zones).  The reference has no
+ * counterpart: it never maps a scene.  The polygons of F features become the int32 zone raster [Hs][Ws] that the zonal statistics
+ * and percentiles above reduce; integers only, so the result depends neither on launch geometry nor on arrival order;
+ * tests/zones_ref.py restates the rule sequentially.  Hs, Ws <= 32767; F <= 2^31 - 1; E <= 2^31 - 1 edges in one table edges_i32
+ * [E][4] = (x0, y0, x1, y1), 16-byte aligned, with edge_feature_i32 [E]; vertices in units of 1/256 pixel, x right and y down, the
+ * centre of pixel (x, y) at (256 x + 128, 256 y + 128), every |coordinate| <= 3 * 32767 * 256.  A horizontal edge crosses no
+ * scanline; any other, oriented so that y0 < y1, crosses the scanlines y with y0 <= 256 y + 128 < y1 and 0 <= y < Hs, at the column
+ * c = clamp(ceil((x0 * dy + (256 y + 128 - y0) * dx - 128 * dy) / (256 * dy)), 0, Ws) with dy = y1 - y0 and dx = x1 - x0, exact in
+ * int64.  The crossing's composite is f << 32 | y << 16 | c; with the X composites sorted ascending, 2k and 2k + 1 bound the span
+ * [c0, c1) of row y of feature f (the edges of a feature form closed rings: the even-odd rule), and zones[y][x] = the smallest f with
+ * a span over (y, x), -1 without one.  Scratch is the caller's: 4 B per edge of counts (scanned in place), two buffers of composites
+ * (16 B per crossing) and the counters of ksmi_scene_quantile_sort, which sorts them with N = F.  Every entry: Hs, Ws outside 0 ..
+ * 32767, E, F, X or n_keys outside 0 .. 2^31 - 1, a misaligned edge table or a null pointer are KSMI_E_ARG and launch nothing.  The
+ * inputs are left unchanged.
+ *   ksmi_scene_zone_rows: the reference has no counterpart.  counts_i32 [E]: the scanlines each edge crosses inside the scene.
+ *   info_i64 [2] is zeroed, then info_i64[0] = the sum of the counts, X, and info_i64[1] = the number of edges refused -- a
+ *   coordinate beyond the bound or a feature outside 0 .. F - 1 -- which count 0.  The exclusive scan of counts_i32 (ksmi_scan_i32;
+ *   X <= 2^31 - 1 is the caller's to check first) gives offsets_i32.  E = 0 zeroes info_i64 and launches nothing. */
+int ksmi_scene_zone_rows(const int32_t* edges_i32, const int32_t* edge_feature_i32, int64_t E, int64_t F, int Hs, int Ws, int32_t* counts_i32,
+                         int64_t* info_i64, void* stream);
+/* ksmi_scene_zone_crossings: the reference has no counterpart.  keys_u64 [n_keys], n_keys >= X: keys_u64[j] = the composite of
+ * crossing j for j < X -- the crossing of edge e = the last one with offsets_i32[e] <= j (a binary search per crossing) with its
+ * scanline number j - offsets_i32[e] --, all ones for j >= X: padding that sorts last, for a sort with F > X rows.  A crossing
+ * whose offsets are no scan of this table's counts is all ones as well.  n_keys = 0 is a no-op. */
+int ksmi_scene_zone_crossings(const int32_t* edges_i32, const int32_t* edge_feature_i32, const int32_t* offsets_i32, int64_t E, int64_t X, int Hs,
+                              int Ws, uint64_t* keys_u64, int64_t n_keys, void* stream);
+/* ksmi_scene_zone_fill: the reference has no counterpart.  zones_i32 [Hs][Ws] is set to -1 (all ones), then every pair sorted_u64[2k],
+ * sorted_u64[2k + 1], k < X / 2, that shares f < F and y < Hs and has c0 < c1 <= Ws lowers zones_i32[y][c0 .. c1) to f with an
+ * unsigned atomic minimum in global memory (one wave64 per span, lanes striding over it): the minimum of integers does not depend on
+ * arrival order.  Any other pair addresses nothing.  X odd is KSMI_E_ARG.  X = 0 or F = 0 still fills the raster with -1; Hs * Ws = 0
+ * is a no-op. */
+int ksmi_scene_zone_fill(const uint64_t* sorted_u64, int64_t X, int64_t F, int Hs, int Ws, int32_t* zones_i32, void* stream);
 
 /* Host half of N4: reader for the archive's GeoTIFF tiles.  The reference decodes each file in a DataLoader worker with
  * cv2.imread(path, cv2.IMREAD_ANYDEPTH) (dataset/Dataset.py:664-728: MS1_IVV/IVH, SL1_*, SL2_*, MK0_MLU, MK0_MNA) and rioxarray

@@ -224,6 +224,9 @@ SIGNATURES = {
     "ksmi_scene_quantile_sort": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "ksmi_scene_quantile_select": (_i, [_vp, _i64, _i64, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp]),
     "ksmi_scene_quantile_segments": (_i, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    "ksmi_scene_zone_rows": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp]),
+    "ksmi_scene_zone_crossings": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _i64, _vp]),
+    "ksmi_scene_zone_fill": (_i, [_vp, _i64, _i64, _i, _i, _vp, _vp]),
     "ksmi_bmm_f32":(_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_float, _i, _vp]),
     "ksmi_softmax_rows_f32": (_i, [_vp, _vp, _i64, _i, C.c_float, _vp]),
     "ksmi_softmax_rows_backward_f32": (_i, [_vp, _vp, _vp, _i64, _i, C.c_float, _vp]),

@@ -19,9 +19,13 @@ total order and a fixed-point sum; integers and min / max only, equal to tests/z
 component labels, so that the depth and the scores meet the polygons: `polygons_geojson(..., attributes=)` joins the rows to the
 features by label.  `zonal_quantiles` (csrc/quantile.hip) sorts a band's finite values per zone -- 64-bit composites of row and value
 key through a stable radix sort, equal to tests/quantile_ref.py -- and selects percentiles on the sorted order; `zonal_sorted` hands
-out the sorted segments themselves and `component_quantiles` keys the percentiles by the component labels.  Everything runs on the
-current stream; nothing synchronises but the three counts (edges, rings, vertices) that `polygonize` reads to size its buffers and
-the one count (zones) that `zonal_stats` and `zonal_quantiles` read to size their tables."""
+out the sorted segments themselves and `component_quantiles` keys the percentiles by the component labels.  `rasterize_zones`
+(csrc/zones.hip) makes the zone raster of a vector layer -- the scanline crossings of the polygons' edges, sorted by the same radix
+sort, paired into spans and written with an integer minimum, equal to tests/zones_ref.py -- from the edge table `zone_edges` or
+`zones_from_geojson` build on the host.  Everything runs on the
+current stream; nothing synchronises but the three counts (edges, rings, vertices) that `polygonize` reads to size its buffers, the
+one count (zones) that `zonal_stats` and `zonal_quantiles` read to size their tables and the one count (crossings) that
+`rasterize_zones` reads."""
 import gc
 import math
 from collections import namedtuple
@@ -48,6 +52,9 @@ MAX_PERCENTILES = 16              # QT_MAX_P of csrc/quantile.hip
 QUANTILE_TILE = 4096              # QT_TILE of csrc/quantile.hip: the composites one workgroup counts and scatters in a radix pass
 ZonalQuantiles = namedtuple("ZonalQuantiles", "zone valid lower higher percentiles")
 QUANTILE_METHODS = ("linear", "lower", "higher", "midpoint", "nearest")
+MAX_ZONE_SIDE = 32767             # ZR_MAX_SIDE of csrc/zones.hip: a scanline and a column each fit 15 bits of a crossing's composite
+MAX_ZONE_COORD = 3 * 32767 * 256  # ZR_MAX_COORD of csrc/zones.hip: vertices in 1/256 pixel; every product of the rule stays under 2^53
+ZoneEdges = namedtuple("ZoneEdges", "edges feature count")
 SCORES = {None: None, "logits": 0, "softmax": 1}
 # test-time view sets, in ascending code; a code's bit 2 transposes the window (first), bit 1 then flips y, bit 0 then flips x
 VIEW_SETS = {"hflip": (0, 1), "flips": (0, 1, 2, 3), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
@@ -914,6 +921,177 @@ def component_quantiles(classes, values, percentiles=(50,), select=(1, 2), label
     if labels is None:
         labels = label_components(classes, 4)
     return zonal_quantiles(labels, values, percentiles, select_classes(classes, select))
+
+
+# ---------------------------------------------------------------------------------------------------- zones from a vector layer
+def rasterize_zones(edges, feature, Hs, Ws, count=None):
+    """The zone raster of a vector layer -> int32 [Hs, Ws] on the device of `edges`: zones[y][x] = the smallest feature whose polygons
+    cover the centre of pixel (x, y), -1 where none does; what zonal_stats and zonal_quantiles take as `zones`.
+
+    edges int32 [E, 4] = (x0, y0, x1, y1) and feature int32 [E], device tensors (ZoneEdges of zone_edges, uploaded): the edges of
+    feature f form closed rings; vertices are in units of 1/256 pixel, x right and y down, the centre of pixel (x, y) at (256 x + 128,
+    256 y + 128), every |coordinate| <= MAX_ZONE_COORD.  Hs, Ws <= 32767.  count: the number of features F (every feature[e] is in
+    0 .. F - 1); None reads max(feature) + 1 on the host, a second read.  The rule, in integers throughout: a horizontal edge crosses
+    no scanline; any other, oriented so that y0 < y1, crosses the scanlines y with y0 <= 256 y + 128 < y1 (half open), kept to 0 <= y <
+    Hs, at the column c = clamp(ceil((x0 * dy + (256 y + 128 - y0) * dx - 128 * dy) / (256 * dy)), 0, Ws): the first column whose
+    centre is at or right of the crossing.  Sorted by (f, y, c), crossings 2k and 2k + 1 bound a span [c0, c1) of row y of feature f:
+    the even-odd rule per feature, so ring orientation does not matter, holes and multipolygon parts need nothing special, a pixel
+    centre exactly on an edge belongs to exactly one side, and features that share an edge partition the pixels along it.  The bits
+    are those of tests/zones_ref.py on every run.  Launches: the scanlines per edge, their scan, one composite f << 32 | y << 16 | c
+    per crossing (its edge found by binary search in the scan), the radix sort of zonal_quantiles with F rows (4 value passes and one
+    per started byte of F - 1), and the fill: the raster set to -1, then one wave64 per span lowering its pixels to f with an integer
+    atomic minimum.  One pair of integers is read on the host: X, the number of crossings, and the number of edges refused (a
+    coordinate beyond the bound, a feature outside 0 .. F - 1: ValueError, as are an odd X -- rings that are not closed -- and X >
+    2^31 - 1).  Scratch: 4 B per edge, 16 B per crossing (two buffers of composites, max(X, F) long) and 1 KiB of counters per 4096
+    crossings.  The inputs are left unchanged.  No edge, no crossing: all -1."""
+    name = "rasterize_zones"
+    if not torch.is_tensor(edges) or edges.dtype != torch.int32 or edges.dim() != 2 or edges.shape[1] != 4 or not edges.is_contiguous():
+        raise ValueError(f"{name}: edges is a contiguous int32 device tensor [E, 4]")
+    if not torch.is_tensor(feature) or feature.dtype != torch.int32 or feature.dim() != 1 or not feature.is_contiguous() \
+            or feature.shape[0] != edges.shape[0] or feature.device != edges.device:
+        raise ValueError(f"{name}: feature is a contiguous int32 vector [E] on the edges' device")
+    for v, what in ((Hs, "Hs"), (Ws, "Ws")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_ZONE_SIDE:
+            raise ValueError(f"{name}: {what} is an int in 0 .. {MAX_ZONE_SIDE}, got {v!r}")
+    if count is not None and (isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 0 <= int(count) <= 2 ** 31 - 1):
+        raise ValueError(f"{name}: count is the number of features, an int in 0 .. 2^31 - 1, got {count!r}")
+    E = edges.shape[0]
+    if E > 2 ** 31 - 1:
+        raise ValueError(f"{name}: at most 2^31 - 1 edges")
+    require_gpu(edges)
+    Hs, Ws, dev = int(Hs), int(Ws), edges.device
+    lib, st = _lib.load(), stream_ptr()
+    F = int(count) if count is not None else (int(feature.max().item()) + 1 if E else 0)
+    zones = torch.empty((Hs, Ws), dtype=torch.int32, device=dev)
+    counts = torch.empty(E, dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    _lib.check(lib.ksmi_scene_zone_rows(edges.data_ptr(), feature.data_ptr(), E, max(F, 0), Hs, Ws, counts.data_ptr(), info.data_ptr(), st),
+               "scene_zone_rows")
+    X, refused = info.tolist()                                          # the one host read
+    if refused:
+        raise ValueError(f"{name}: {refused} edges with a coordinate beyond +-{MAX_ZONE_COORD} or a feature outside 0 .. {F - 1}")
+    if X > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {X} crossings, more than 2^31 - 1")
+    if X % 2:
+        raise ValueError(f"{name}: an odd number of crossings ({X}): the edges of a feature do not form closed rings")
+    ordered = None
+    if X and Hs * Ws:
+        _scan(counts, counts, "scan_i32")
+        n_keys = max(X, F)                                              # the sort takes no more rows than composites: all ones pad them
+        keys, alt = torch.empty(n_keys, dtype=torch.int64, device=dev), torch.empty(n_keys, dtype=torch.int64, device=dev)
+        need = int(lib.ksmi_scene_quantile_scratch(n_keys))
+        scratch = torch.empty(need, dtype=torch.int32, device=dev)
+        _lib.check(lib.ksmi_scene_zone_crossings(edges.data_ptr(), feature.data_ptr(), counts.data_ptr(), E, X, Hs, Ws, keys.data_ptr(), n_keys,
+                                                 st), "scene_zone_crossings")
+        _lib.check(lib.ksmi_scene_quantile_sort(keys.data_ptr(), alt.data_ptr(), n_keys, F, scratch.data_ptr(), need, st), "scene_quantile_sort")
+        ordered = keys if int(lib.ksmi_scene_quantile_passes(F)) % 2 == 0 else alt
+    _lib.check(lib.ksmi_scene_zone_fill(None if ordered is None else ordered.data_ptr(), X if ordered is not None else 0, F, Hs, Ws,
+                                        zones.data_ptr(), st), "scene_zone_fill")
+    return zones
+
+
+def _clip_ring(p, x_lo, x_hi, y_lo, y_hi):
+    """Sutherland-Hodgman: the ring p float64 [n, 2] against the box, in the order left, right, top, bottom.  An intersection is
+    computed from the edge's lexicographically smaller end, so an edge shared by two rings is cut at the same point in both."""
+    for axis, bound, keep_above in ((0, x_lo, True), (0, x_hi, False), (1, y_lo, True), (1, y_hi, False)):
+        if p.shape[0] == 0:
+            break
+        a, b = p, np.roll(p, -1, axis=0)
+        ina = a[:, axis] >= bound if keep_above else a[:, axis] <= bound
+        inb = np.roll(ina, -1)
+        swap = (a[:, 0] > b[:, 0]) | ((a[:, 0] == b[:, 0]) & (a[:, 1] > b[:, 1]))
+        lo, hi = np.where(swap[:, None], b, a), np.where(swap[:, None], a, b)
+        cut = ina != inb                                                # there lo and hi differ along the axis
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (bound - lo[:, axis]) / (hi[:, axis] - lo[:, axis])
+            hit = lo + t[:, None] * (hi - lo)                           # used only where cut
+        hit[:, axis] = bound
+        both = np.empty((p.shape[0], 2, 2), np.float64)                 # per edge: its start if inside, then its cut
+        both[:, 0], both[:, 1] = a, hit
+        p = both[np.stack((ina, cut), axis=1)]
+    return p
+
+
+def zone_edges(features, Hs, Ws, pixel_scale=None, origin=None):
+    """The edge table of a vector layer for rasterize_zones, on the host -> ZoneEdges(edges int32 [E, 4], feature int32 [E], count),
+    numpy arrays; count = len(features).
+
+    features: a list with one list of rings per feature (exterior rings, holes and multipolygon parts alike: the even-odd rule needs
+    no distinction); a ring is a sequence of (X, Y) or (X, Y, Z) map coordinates, closed or not.  In float64 px = (X - ox) / sx and py
+    = (oy - Y) / sy with pixel_scale = (sx, sy) and origin = (ox, oy) as geotiff.read returns them: the inverse of what
+    polygons_geojson writes (scale (1, 1) and origin (0, 0) without georeferencing).  A closing vertex equal to the first is dropped.
+    A ring that leaves the box [-Ws, 2 Ws] x [-Hs, 2 Hs] is clipped against it (Sutherland-Hodgman: left, right, top, bottom); a ring
+    inside the box is untouched.  Then q = rint(256 p), half to even, in units of 1/256 pixel, so every vertex is within the
+    coordinate bound of rasterize_zones.  A ring of fewer than 3 vertices gives no edge.  A clipped ring is accurate to 1/256 pixel,
+    like any vertex: where an edge is cut, its new end is rounded as every vertex is, and the edge may move by that much."""
+    for v, what in ((Hs, "Hs"), (Ws, "Ws")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_ZONE_SIDE:
+            raise ValueError(f"zone_edges: {what} is an int in 0 .. {MAX_ZONE_SIDE}, got {v!r}")
+    sx, sy = (1.0, 1.0) if pixel_scale is None else (float(pixel_scale[0]), float(pixel_scale[1]))
+    ox, oy = (0.0, 0.0) if origin is None else (float(origin[0]), float(origin[1]))
+    Hs, Ws = int(Hs), int(Ws)
+    tables, owners = [], []
+    for f, rings in enumerate(features):
+        for ring in rings:
+            a = np.asarray(ring, np.float64)
+            if a.size == 0:
+                continue
+            if a.ndim != 2 or a.shape[1] < 2:
+                raise ValueError(f"zone_edges: a ring of feature {f} is no sequence of (X, Y) positions")
+            p = np.stack(((a[:, 0] - ox) / sx, (oy - a[:, 1]) / sy), axis=1)
+            if not np.isfinite(p).all():
+                raise ValueError(f"zone_edges: a ring of feature {f} has a coordinate that is not finite")
+            if p.shape[0] > 1 and (p[0] == p[-1]).all():
+                p = p[:-1]
+            if (p[:, 0] < -Ws).any() or (p[:, 0] > 2 * Ws).any() or (p[:, 1] < -Hs).any() or (p[:, 1] > 2 * Hs).any():
+                p = _clip_ring(p, -float(Ws), 2.0 * Ws, -float(Hs), 2.0 * Hs)
+            q = np.rint(256.0 * p).astype(np.int64)
+            if q.shape[0] < 3:
+                continue
+            tables.append(np.concatenate((q, np.roll(q, -1, axis=0)), axis=1))
+            owners.append(np.full(q.shape[0], f, np.int64))
+    edges = np.concatenate(tables, axis=0) if tables else np.empty((0, 4), np.int64)
+    owner = np.concatenate(owners) if owners else np.empty(0, np.int64)
+    return ZoneEdges(np.ascontiguousarray(edges.astype(np.int32)), np.ascontiguousarray(owner.astype(np.int32)), len(features))
+
+
+def zones_from_geojson(obj, Hs, Ws, pixel_scale=None, origin=None, key=None):
+    """A GeoJSON object (a dict: a FeatureCollection, a Feature or a bare geometry) -> (ZoneEdges, ids) through zone_edges.
+
+    Feature f of the file is row f: a Polygon gives its rings, a MultiPolygon the rings of all its parts, any other geometry and a
+    null geometry keep their index with no ring (and so no pixel).  Z values are ignored.  A "crs" member is ignored with a printed
+    note: coordinates are taken in the raster's own coordinate reference system, as polygons_geojson writes them.  ids[f] =
+    properties[key], or f when key is None."""
+    name = "zones_from_geojson"
+    if not isinstance(obj, dict) or "type" not in obj:
+        raise ValueError(f"{name}: a GeoJSON object (a dict with a \"type\")")
+    if "crs" in obj:
+        print(f"{name}: the \"crs\" member is ignored: coordinates are taken in the raster's own coordinate reference system")
+    if obj["type"] == "FeatureCollection":
+        members = list(obj.get("features") or [])
+    elif obj["type"] == "Feature":
+        members = [obj]
+    else:
+        members = [{"type": "Feature", "properties": {}, "geometry": obj}]
+    features, ids = [], []
+    for f, member in enumerate(members):
+        geometry = member.get("geometry") if isinstance(member, dict) else None
+        kind = geometry.get("type") if isinstance(geometry, dict) else None
+        if kind == "Polygon":
+            rings = list(geometry.get("coordinates") or [])
+        elif kind == "MultiPolygon":
+            rings = [ring for part in geometry.get("coordinates") or [] for ring in part]
+        else:
+            rings = []
+        features.append(rings)
+        if key is None:
+            ids.append(f)
+        else:
+            properties = member.get("properties") if isinstance(member, dict) else None
+            if not isinstance(properties, dict) or key not in properties:
+                raise ValueError(f"{name}: feature {f} has no property {key!r}")
+            ids.append(properties[key])
+    return zone_edges(features, Hs, Ws, pixel_scale, origin), ids
 
 
 # ---------------------------------------------------------------------------------------------------- the scene loop

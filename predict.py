@@ -7,7 +7,8 @@
       [--window 224 --stride 112 --weight hann --batch_size 32 --precision bf16] [--tta hflip] \\
       [--mmu 12 --connectivity 4 --sieve_passes 1] [--report flood.json] \\
       [--polygons flood.geojson --polygon_classes 1 2] [--components components.csv] \\
-      [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2] [--percentiles 50 90]]
+      [--depth_out depth.tif [--depth_dem dem.tif] [--depth_classes 1 2] [--percentiles 50 90]] \\
+      [--zones districts.geojson [--zone_key NAME] [--zones_out zones.csv] [--zones_raster zones.tif] [--zone_classes 1 2]]
 
 Each date takes one or more GeoTIFFs whose bands are concatenated in the order given; all rasters have one size.  The file's own
 nodata tag is the sentinel of its date (--nodata overrides it); a pixel where any input is NaN or the sentinel becomes class 3
@@ -74,9 +75,29 @@ percentile after "volume": "depth_p" and the percent with trailing zeros strippe
 the percentile over the component's pixels with a finite depth, interpolated linearly between the two neighbouring sorted values in
 float64 as np.percentile does (the position c * (n - 1) / 10000 taken in exact integers); null for a component without such a
 pixel.  The "depth" key of --report gains "percentiles": {"p50": ..., "p90": ...} over all pixels of --depth_classes with a finite
-depth (one zone: the whole water surface); null values without such a pixel.  Percentiles of the confidence, weighted percentiles
-and zones from a vector layer are outside this tool."""
+depth (one zone: the whole water surface); null values without such a pixel.  Percentiles of the confidence and weighted
+percentiles are outside this tool.
+
+--zones FILE.geojson describes the map as written (after --mmu) per feature of a vector layer -- districts, parcels, river reaches --
+and needs one of --zones_out, --zones_raster, --report.  The file is a FeatureCollection, a Feature or a bare geometry; Polygon and
+MultiPolygon features give zones, any other and a null geometry keep their index without a pixel, so zone f is always feature f of
+the file.  Coordinates are taken in the raster's own coordinate reference system through the first post file's georeferencing
+(pixel coordinates with y negated without one), the inverse of what --polygons writes; a "crs" member is ignored with a note.  The
+polygons are rasterised on the device (kurosiwo_amd.scene.zones_from_geojson, rasterize_zones): a pixel belongs to the first feature
+whose polygons cover its centre under the even-odd rule, decided in integers at 1/256 pixel, so features that share an edge
+partition the pixels along it; the rasters are still on the device, and every number below comes from
+kurosiwo_amd.scene.zonal_stats and zonal_quantiles keyed by that zone raster.  More features than scene pixels are refused.
+--zones_out FILE.csv has one row per feature in file order; a feature without a pixel gets zeros and empty cells.  The header row is
+  zone,id,pixels,valid,class_0,class_1,class_2,class_3,flooded,flooded_area,flooded_fraction
+zone is the feature's index and id its property --zone_key (the index without one); pixels counts the zone's pixels in the scene and
+valid those not of class 3; flooded counts the pixels of --zone_classes (default 1 2), flooded_area = flooded * "pixel_area" (empty
+without georeferencing) and flooded_fraction = flooded / valid (empty when valid is 0).  With --depth_out follow
+,depth_pixels,depth_max,depth_mean,volume over the zone's pixels of --depth_classes, as in --components, and with --percentiles the
+depth_pNN columns.  --zones_raster FILE.tif writes the zone raster itself: int32, nodata -1, Deflate in tiles of 256.  --report gains
+a key "zones": "features", "with_pixels" (those with a pixel in the scene) and "pixels" (the scene's pixels in any zone).
+Reprojection of the layer, line and point features, an all-touched rule and fractional coverage are outside this tool."""
 import argparse
+import csv
 import json
 import os
 import sys
@@ -93,8 +114,8 @@ from kurosiwo_amd import geotiff                                            # no
 from kurosiwo_amd.config import load_json5, update_config                   # noqa: E402
 from kurosiwo_amd.model_utilities import initialize_cd_model, initialize_segmentation_model      # noqa: E402
 from kurosiwo_amd.scene import (basis_points, cd_forward, component_quantiles, component_stats, flood_depth, label_components,      # noqa: E402
-                                percentile_name, polygonize, polygons_geojson, predict_scene, quantile_values, seg_forward, select_classes,
-                                sieve, zonal_geometry, zonal_quantiles)
+                                percentile_name, polygonize, polygons_geojson, predict_scene, quantile_values, rasterize_zones, seg_forward,
+                                select_classes, sieve, zonal_geometry, zonal_quantiles, zonal_stats, zones_from_geojson)
 
 CD_METHODS = ("snunet", "changeformer", "siam-conc", "siam-diff", "bit-cd")
 
@@ -133,6 +154,11 @@ parser.add_argument("--depth_dem", default=None, help="the DEM the depth is take
 parser.add_argument("--depth_classes", type=int, nargs="+", default=[1, 2])
 parser.add_argument("--percentiles", type=float, nargs="+", default=None,
                     help="percents (50 90 97.5): percentiles of the depth per component and over all water; needs --depth_out and a table")
+parser.add_argument("--zones", default=None, help="FILE.geojson: polygons (districts, parcels) to describe the map as written by")
+parser.add_argument("--zone_key", default=None, help="the property that names a feature of --zones (default: its index)")
+parser.add_argument("--zones_out", default=None, help="FILE.csv: one row of statistics per feature of --zones")
+parser.add_argument("--zones_raster", default=None, help="FILE.tif: the int32 zone raster of --zones, nodata -1")
+parser.add_argument("--zone_classes", type=int, nargs="+", default=[1, 2], help="the classes counted as flooded per zone")
 
 
 def read_date(paths, nodata):
@@ -233,6 +259,63 @@ def write_components(path, zonal, cols):
             f.write(",".join([str(z)] + [cell(cols[k][r]) for k in names]) + "\n")
 
 
+ZONE_COLUMNS = ("zone", "id", "pixels", "valid", "class_0", "class_1", "class_2", "class_3", "flooded", "flooded_area", "flooded_fraction")
+
+
+def zone_table(zones, ids, classes, flooded, area, depth, depth_classes, percents=None):
+    """the statistics of the F = len(ids) features of the device zone raster `zones` over the device map `classes` -> {column: one
+    value per feature}: the columns of --zones_out, in order; depth (device float32 [Hs, Ws] or None) adds DEPTH_COLUMNS over the
+    pixels of depth_classes and, with `percents`, one column per percentile.  Every number is a row of zonal_stats or
+    zonal_quantiles put at its zone id; a feature without a row keeps zeros and nulls.  None is a null."""
+    F = len(ids)
+
+    def spread(zone, column, fill=0):
+        out = [fill] * F
+        for z, v in zip(zone.cpu().numpy().tolist(), column.cpu().numpy().tolist()):
+            out[z] = v
+        return out
+
+    def pixels_of(where):
+        rows = zonal_stats(zones, None, where)
+        return spread(rows.zone, rows.count)
+
+    per_class = [pixels_of(select_classes(classes, (k,))) for k in range(4)]
+    cols = {"zone": list(range(F)), "id": list(ids), "pixels": pixels_of(None)}
+    cols["valid"] = [n - k for n, k in zip(cols["pixels"], per_class[3])]
+    cols.update((f"class_{k}", per_class[k]) for k in range(4))
+    cols["flooded"] = pixels_of(select_classes(classes, flooded))
+    cols["flooded_area"] = [None if area is None else n * area for n in cols["flooded"]]
+    cols["flooded_fraction"] = [n / v if v else None for n, v in zip(cols["flooded"], cols["valid"])]
+    if depth is not None:
+        water = select_classes(classes, depth_classes)
+        deep = zonal_stats(zones, depth, water, frac_bits=DEPTH_FRAC_BITS)
+        n, top = spread(deep.zone, deep.valid[0]), spread(deep.zone, deep.vmax[0], 0.0)
+        metres = [v / float(2 ** DEPTH_FRAC_BITS) for v in spread(deep.zone, deep.vsum[0])]
+        cols["depth_pixels"] = n
+        cols["depth_max"] = [float(v) if k else None for v, k in zip(top, n)]
+        cols["depth_mean"] = [m / k if k else None for m, k in zip(metres, n)]
+        cols["volume"] = [None if area is None else m * area for m in metres]
+        if percents:
+            zq = zonal_quantiles(zones, depth, percents, water)
+            assert torch.equal(zq.zone, deep.zone) and torch.equal(zq.valid, deep.valid)
+            for name, column in zip(percentile_columns(zq.percentiles), percentile_cells(zq)):
+                cols[name] = [None] * F
+                for z, v in zip(zq.zone.cpu().numpy().tolist(), column):
+                    cols[name][z] = v
+    return cols
+
+
+def write_zones(path, cols):
+    """--zones_out: the header row, then one row per feature; cells as in --components, quoted where an id needs it"""
+    names = list(cols)
+    cell = lambda v: "" if v is None else repr(v) if isinstance(v, float) else str(v)
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f, lineterminator="\n")
+        out.writerow(names)
+        for r in range(len(cols["zone"])):
+            out.writerow([cell(cols[k][r]) for k in names])
+
+
 def load_model(configs, model_configs, checkpoint):
     if configs["task"] == "cd":
         configs["resume_checkpoint"] = checkpoint
@@ -270,6 +353,16 @@ def main(argv=None):
             raise SystemExit(str(e)) from None
         if len(set(pcts)) != len(pcts):
             raise SystemExit("predict.py: --percentiles names a percentile twice")
+    if args.zones is None and (args.zone_key is not None or args.zones_out is not None or args.zones_raster is not None):
+        raise SystemExit("predict.py: --zone_key, --zones_out and --zones_raster need --zones")
+    if args.zones is not None and args.zones_out is None and args.zones_raster is None and args.report is None:
+        raise SystemExit("predict.py: --zones needs one of --zones_out, --zones_raster, --report")
+    if any(not 0 <= c <= 62 for c in args.zone_classes):
+        raise SystemExit("predict.py: --zone_classes takes class values 0 .. 62")
+    layer = None
+    if args.zones is not None:
+        with open(args.zones) as f:
+            layer = json.load(f)
     method = args.method.lower()
     task = args.task or ("cd" if method in CD_METHODS else "segmentation")
     dates = [(n, p) for n, p in (("pre_event_1", args.pre1), ("pre_event_2", args.pre2)) if p]
@@ -363,6 +456,29 @@ def main(argv=None):
     if args.components is not None:
         write_components(args.components, zonal, cols)
         print(f"wrote {args.components}: {zonal.zone.numel()} components of classes {' '.join(str(c) for c in args.polygon_classes)}")
+    zones_report = None
+    if layer is not None:                               # on the map as written, the rasters still on the device
+        try:
+            table, zone_ids = zones_from_geojson(layer, classes.shape[0], classes.shape[1], geo["pixel_scale"], geo["origin"], key=args.zone_key)
+        except ValueError as e:
+            raise SystemExit(f"predict.py: --zones: {e}") from None
+        if table.count > classes.numel():
+            raise SystemExit(f"predict.py: --zones has {table.count} features, the scene {classes.numel()} pixels: more zones than pixels "
+                             "cannot be told apart")
+        zones = rasterize_zones(torch.from_numpy(table.edges).to(dev), torch.from_numpy(table.feature).to(dev), classes.shape[0],
+                                classes.shape[1], count=table.count)
+        if args.zones_raster is not None:
+            geotiff.write(args.zones_raster, zones.cpu().numpy(), nodata=-1, **where)
+            print(f"wrote {args.zones_raster}: the zones of {table.count} features")
+        if args.zones_out is not None:
+            zcols = zone_table(zones, zone_ids, classes, args.zone_classes, area, depth_dev, args.depth_classes, args.percentiles if pcts else None)
+            assert tuple(zcols) == ZONE_COLUMNS + (DEPTH_COLUMNS + percentile_columns(pcts) if depth_dev is not None else ())
+            write_zones(args.zones_out, zcols)
+            inside = zcols["pixels"]
+            print(f"wrote {args.zones_out}: {table.count} zones, flooded classes {' '.join(str(c) for c in args.zone_classes)}")
+        else:
+            inside = zonal_stats(zones).count.cpu().numpy().tolist()
+        zones_report = {"features": table.count, "with_pixels": sum(1 for n in inside if n), "pixels": int(sum(inside))}
     if args.report is not None:
         counts = np.bincount(written.ravel(), minlength=4).tolist()
         report = {"pixel_counts": counts, "pixel_area": area, "class_area": None if area is None else [area * c for c in counts],
@@ -373,6 +489,8 @@ def main(argv=None):
             sizes, ids = cols["pixels"], zonal.zone.cpu().numpy().tolist()
             top = int(np.argmax(sizes)) if sizes else None                # the first maximum: the smallest label on a tie
             report["components"] = {"count": len(ids), "largest": None if top is None else {"label": ids[top], "pixels": sizes[top]}}
+        if zones_report is not None:
+            report["zones"] = zones_report
         with open(args.report, "w") as f:
             json.dump(report, f, indent=1)
         print(f"wrote {args.report}")

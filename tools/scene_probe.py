@@ -2,6 +2,7 @@
 
     python tools/scene_probe.py [--size 4480] [--window 224] [--stride 112] [--batch 32] [--precision bf16] [--repeats 5] [--out FILE]
                                 [--mmu N [--connectivity 4] [--sieve_only]] [--polygons [--polygons_only]] [--tta SET [SET ...]] [--depth] [--zonal] [--quantiles]
+                                [--zones]
 
 A synthetic size x size scene with two dates of 2 channels (seeded, NaNs planted), SNUNet-ECAM (base_channel 32) in eval mode.
 After one warm-up pass (code objects, the plans of the full and of the ragged batch) every figure is the median of `repeats` passes:
@@ -58,6 +59,15 @@ After one warm-up pass (code objects, the plans of the full and of the ragged ba
              with torch ops only: the presence flags by index_fill_, their cumsum and the read of N, int64 composites, torch.sort,
              torch.searchsorted for the segment bounds and a gather; its valid, lower and higher are checked equal to
              zonal_quantiles' bit for bit.
+  zones      with --zones (the numbers behind profiles/zones_probe.txt), instead of the passes above: kurosiwo_amd.scene.rasterize_zones
+             on a size x size scene for three vector layers -- one polygon over the whole scene (4 edges, spans as long as a row), a
+             100 x 100 grid of squares turned by 10 degrees about the middle (shared edges, spans of about 45 pixels), and the rings
+             polygonize gives for speckle_scene of tests/sieve_ref.py, rasterised back (millions of spans of a pixel or two; the
+             result is checked against the component labels).  Per layer: the event time of rasterize_zones end to end, the number
+             of radix passes, and the event time of each stage of the same sequence: rows (ksmi_scene_zone_rows and the read of X),
+             scan (ksmi_scan_i32), crossings (ksmi_scene_zone_crossings), sort (ksmi_scene_quantile_sort), fill
+             (ksmi_scene_zone_fill: the memset and the spans); then, in the same call, the zonal_stats call that follows it (no
+             value band).
 One json object per line on stdout, appended to --out when given."""
 import argparse
 import json
@@ -88,6 +98,7 @@ def main():
     ap.add_argument("--depth", action="store_true", default=False)
     ap.add_argument("--zonal", action="store_true", default=False)
     ap.add_argument("--quantiles", action="store_true", default=False)
+    ap.add_argument("--zones", action="store_true", default=False)
     ap.add_argument("--tta", nargs="+",choices=("none", "hflip", "flips", "d4"), default=None)
     a = ap.parse_args()
     import numpy as np
@@ -121,6 +132,9 @@ def main():
         return finish()
     if a.quantiles:
         quantile_probe(a, emit, ev, med)
+        return finish()
+    if a.zones:
+        zones_probe(a, emit, ev, med)
         return finish()
     if a.mmu is not None:
         sieve_probe(a, emit, ev, med)
@@ -631,6 +645,114 @@ def quantile_probe(a, emit, ev, med):
              zonal_quantiles_ms=round(med(ours), 3), torch_sort_route_ms=round(med(theirs), 3), ratio=round(med(ours) / med(theirs), 3),
              **{k + "_ms": round(x, 3) for k, x in zip(stages, t)}, staged_total_ms=round(sum(t), 3))
         del d, labels, where, v, first, whole, again
+
+
+def zones_probe(a, emit, ev, med):
+    """rasterize_zones on three vector layers over a.size x a.size, timed whole and per stage, and the zonal_stats call after it"""
+    import numpy as np
+    import torch
+    from kurosiwo_amd import _lib, scene
+    from kurosiwo_amd.runtime import stream_ptr
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import sieve_ref
+    S, lib, st = a.size, _lib.load(), stream_ptr()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    chk = _lib.check
+    stages = ("rows", "scan", "crossings", "sort", "fill")
+
+    def timed(fn):
+        e0, e1 = ev(), ev()
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    def staged(edges, feature, F):
+        E = edges.shape[0]
+        zones = torch.empty((S, S), dtype=torch.int32, device="cuda")
+        counts = torch.empty(E, dtype=torch.int32, device="cuda")
+        info = torch.empty(2, dtype=torch.int64, device="cuda")
+        total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        scan_need = int(lib.ksmi_scan_i32_scratch(E))
+        scratch = torch.empty(max(scan_need, 1), dtype=torch.int32, device="cuda")
+        e = [ev() for _ in range(6)]
+        e[0].record()
+        chk(lib.ksmi_scene_zone_rows(ptr(edges), ptr(feature), E, F, S, S, ptr(counts), ptr(info), st), "scene_zone_rows")
+        X, refused = info.tolist()                                             # the one host read
+        assert not refused and X % 2 == 0 and 0 < X < 2 ** 31
+        e[1].record()
+        chk(lib.ksmi_scan_i32(ptr(counts), ptr(counts), E, ptr(total), ptr(scratch), scan_need, st), "scan_i32")
+        e[2].record()
+        n_keys = max(X, F)
+        keys, alt = (torch.empty(n_keys, dtype=torch.int64, device="cuda") for _ in range(2))
+        sort_need = int(lib.ksmi_scene_quantile_scratch(n_keys))
+        counters = torch.empty(sort_need, dtype=torch.int32, device="cuda")
+        chk(lib.ksmi_scene_zone_crossings(ptr(edges), ptr(feature), ptr(counts), E, X, S, S, ptr(keys), n_keys, st), "scene_zone_crossings")
+        e[3].record()
+        chk(lib.ksmi_scene_quantile_sort(ptr(keys), ptr(alt), n_keys, F, ptr(counters), sort_need, st), "scene_quantile_sort")
+        e[4].record()
+        ordered = keys if lib.ksmi_scene_quantile_passes(F) % 2 == 0 else alt
+        chk(lib.ksmi_scene_zone_fill(ptr(ordered), X, F, S, S, ptr(zones), st), "scene_zone_fill")
+        e[5].record()
+        torch.cuda.synchronize()
+        lengths = (ordered[1:X:2] & 0xFFFF) - (ordered[0:X:2] & 0xFFFF)
+        return [e[j].elapsed_time(e[j + 1]) for j in range(5)], zones, X, float(lengths.double().mean())
+
+    def ring_layer(rings):
+        """the ring table of polygonize as an edge table, vertices times 256, one feature per component in ascending label"""
+        V = rings.verts.shape[0]
+        k = torch.arange(V, dtype=torch.int64, device="cuda")
+        start = rings.start.long()
+        ring = torch.searchsorted(start[1:].contiguous(), k, right=True)
+        nxt = torch.where(k + 1 == start[1:][ring], start[:-1][ring], k + 1)
+        labels, rank = torch.unique(rings.label, return_inverse=True)
+        edges = (torch.cat((rings.verts, rings.verts[nxt]), dim=1) * 256).contiguous()
+        return edges, rank[ring].to(torch.int32).contiguous(), int(labels.numel()), labels
+
+    layers = {}
+    rect = np.array([[-256, -256], [S * 256 + 256, -256], [S * 256 + 256, S * 256 + 256], [-256, S * 256 + 256]], np.int64)
+    layers["one_polygon"] = (np.concatenate((rect, np.roll(rect, -1, axis=0)), axis=1).astype(np.int32), np.zeros(4, np.int32), 1)
+    n, turn = 100, np.deg2rad(10.0)
+    gy, gx = np.mgrid[0:n + 1, 0:n + 1].astype(np.float64) * (S / n) - S / 2.0
+    px, py = S / 2.0 + gx * np.cos(turn) - gy * np.sin(turn), S / 2.0 + gx * np.sin(turn) + gy * np.cos(turn)
+    q = np.rint(256.0 * np.stack((px, py), axis=2)).astype(np.int64)           # shared corners round once: the squares partition
+    quad = np.stack((q[:-1, :-1], q[:-1, 1:], q[1:, 1:], q[1:, :-1]), axis=2).reshape(n * n, 4, 2)
+    layers["grid_100x100_turned_10"] = (np.concatenate((quad, np.roll(quad, -1, axis=1)), axis=2).reshape(-1, 4).astype(np.int32),
+                                        np.repeat(np.arange(n * n), 4).astype(np.int32), n * n)
+    classes = torch.from_numpy(sieve_ref.speckle_scene(4480, S, S)).cuda()
+    rings = scene.polygonize(classes)
+    edges, feature, F, labels = ring_layer(rings)
+    layers["speckle_rings"] = (edges, feature, F)
+    boundary_edges = int(scene.boundary_edges(classes, scene.label_components(classes, 4))[0].numel())
+    del rings
+
+    for name, (edges, feature, F) in layers.items():
+        if not torch.is_tensor(edges):
+            edges, feature = torch.from_numpy(edges).cuda(), torch.from_numpy(feature).cuda()
+        _, first, X, mean_span = staged(edges, feature, F)                     # warm-up
+        whole = scene.rasterize_zones(edges, feature, S, S, count=F)
+        assert torch.equal(first, whole)                                       # the staged sequence is rasterize_zones
+        if name == "speckle_rings":                                            # back to the components they were traced from
+            lab = scene.label_components(classes, 4)
+            rank = torch.searchsorted(labels, lab).to(torch.int32)
+            assert torch.equal(whole, torch.where(scene.select_classes(classes, (1, 2)) != 0, rank, torch.full_like(rank, -1)))
+            del lab, rank
+        scene.zonal_stats(whole)                                               # warm-up
+        ours, after, split = [], [], []
+        for _ in range(a.repeats):
+            ours.append(timed(lambda: scene.rasterize_zones(edges, feature, S, S, count=F))[0])
+            after.append(timed(lambda: scene.zonal_stats(whole))[0])
+            t, again, _, _ = staged(edges, feature, F)
+            split.append(t)
+        assert torch.equal(first, again)                                       # equal bits
+        t = [med(r[j] for r in split) for j in range(5)]
+        emit(what="zones", content=name, size=S, edges=int(edges.shape[0]), features=F, crossings=X, spans=X // 2,
+             mean_span_pixels=round(mean_span, 2), pixels_in_a_zone=int((whole >= 0).sum()), radix_passes=int(lib.ksmi_scene_quantile_passes(F)),
+             **({"unit_boundary_edges": boundary_edges} if name == "speckle_rings" else {}),
+             rasterize_zones_ms=round(med(ours), 3), **{k + "_ms": round(x, 3) for k, x in zip(stages, t)}, staged_total_ms=round(sum(t), 3),
+             zonal_stats_after_ms=round(med(after), 3))
+        del edges, feature, first, whole, again
 
 
 def sieve_probe(a, emit, ev, med):
