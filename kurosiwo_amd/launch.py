@@ -18,17 +18,6 @@ def _tag_id(tag):
     return _TAG_IDS.setdefault(tag, len(_TAG_IDS))
 
 
-def _sig_codes(argtypes):
-    """signature string of tools/gen_thunks.py: one letter per argument (p pointer, i int, u unsigned, l int64, z size_t, f float, d double)"""
-    out = []
-    for t in argtypes:
-        if t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and (issubclass(t, C._Pointer) or issubclass(t, C.Array))):
-            out.append("p")
-        else:
-            out.append({C.c_int: "i", C.c_int32: "i", C.c_uint32: "u", C.c_int64: "l", C.c_size_t: "z", C.c_float: "f", C.c_double: "d"}[t])
-    return "".join(out)
-
-
 def _slot(code, v, struct):
     """one prepared argument as the 64-bit slot the call thunks read (include/ksmi.h ksmi_op)"""
     if hasattr(v, "value") and not hasattr(v, "_obj"):        # a ctypes scalar (c_void_p, c_int, ...)
@@ -133,7 +122,7 @@ class LaunchList:
                 ok = False
                 continue
             restype, argtypes = _lib.SIGNATURES[name]
-            codes = _sig_codes(argtypes[:-1])
+            codes = _lib.sig_codes(argtypes[:-1])
             sig = lib.ksmi_thunk_id(codes.encode())
             if sig < 0 or len(codes) != len(args):
                 raise _lib.KsmiError(f"launch list: no call thunk for {name} ({codes!r}, {len(args)} arguments): re-run tools/gen_thunks.py")

@@ -24,6 +24,25 @@ def test_library_exports_every_declared_symbol():
     assert lib.ksmi_chunk_elems(_lib.KSMI_BF16) == 32 and lib.ksmi_chunk_elems(_lib.KSMI_F32) == 16
 
 
+def test_every_entry_point_is_bound_as_the_header_declares_it():
+    """over EVERY entry point, with a reading of the header that shares nothing with kurosiwo_amd/_abi.py: exported, the arity of
+    the declaration, and int status with the stream last (= listable by the executor) exactly where the header says so"""
+    import ctypes as C
+    lib = _lib.load()
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ksmi.h")).read(), flags=re.S)
+    listable = _lib.ABI.listable()
+    decls = re.findall(r"([\w \t*]+?)\b(ksmi_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(decls) == len(_lib.SIGNATURES) == 207
+    for ret, name, params in decls:
+        res, args = _lib.SIGNATURES[name]
+        assert hasattr(lib, name), name
+        assert len(args) == (0 if params.strip() == "void" else len(params.split(","))), name
+        status_and_stream = ret.split() == ["int"] and params.split(",")[-1].split() == ["void*", "stream"]
+        assert status_and_stream == (name in listable), name
+        if status_and_stream:
+            assert res is C.c_int and args[-1] is C.c_void_p and len(listable[name]) == len(args) - 1, name
+
+
 def test_struct_sizes_match_header_layout():
     import ctypes as C
     assert C.sizeof(_lib.Src) == 40 and C.sizeof(_lib.Dst) == 32 and _lib.MAX_CHUNKS == 72

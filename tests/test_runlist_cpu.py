@@ -1,5 +1,5 @@
 """Host side of the launch-list executor (csrc/runlist.hip, include/ksmi.h ksmi_run_list): the generated call thunks are in step with
-the binding table, every entry point a plan may list has one, and the argument slots carry the values the thunks read.  The executor
+the binding derived from the header, every entry point a plan may list has one, and the argument slots carry the values the thunks read.  The executor
 itself is exercised end to end by the GPU tests (tests/test_gpu_graph.py: compiled list == Python walk, bit for bit); here a one-entry
 list calls a host-only entry point through it (ksmi_tiles_fill_nodata takes no stream... so the CALL path is covered on the GPU only)."""
 import ctypes as C
@@ -20,13 +20,11 @@ def test_generated_thunks_are_current():
 
 def test_every_listable_entry_point_has_a_thunk():
     lib = _lib.load()
-    n = 0
-    for name, (res, args) in _lib.SIGNATURES.items():
-        if res is C.c_int and args and args[-1] is C.c_void_p and not name.startswith(("ksmi_runner_", "ksmi_run_list", "ksmi_thunk_")):
-            codes = sp._sig_codes(args[:-1])
-            assert lib.ksmi_thunk_id(codes.encode()) >= 0, (name, codes)
-            n += 1
-    assert n > 100
+    listable = _lib.ABI.listable()                  # int status, stream last
+    for name, codes in listable.items():
+        assert codes == _lib.sig_codes(_lib.SIGNATURES[name][1][:-1])
+        assert lib.ksmi_thunk_id(codes.encode()) >= 0, (name, codes)
+    assert len(listable) > 100 and not any(n.startswith(("ksmi_runner_", "ksmi_run_list", "ksmi_thunk_")) for n in listable)
     assert lib.ksmi_thunk_id(b"no-such-signature") == -1
 
 
@@ -42,7 +40,7 @@ def test_argument_slots():
     assert sp._slot("l", -(1 << 40), struct) == (1 << 64) - (1 << 40)
     assert sp._slot("f", 1.5, struct) == 0x3FC00000
     assert sp._slot("d", -2.0, struct) == 0xC000000000000000
-    assert sp._sig_codes([C.c_void_p, C.POINTER(_lib.ConvDesc), C.c_void_p * 4, C.c_int, C.c_int64, C.c_size_t, C.c_uint32, C.c_float, C.c_double]) == "pppilzufd"
+    assert _lib.sig_codes([C.c_void_p, C.POINTER(_lib.ConvDesc), C.c_void_p * 4, C.c_int, C.c_int64, C.c_size_t, C.c_uint32, C.c_float, C.c_double]) == "pppilzufd"
 
 
 def test_runner_lifecycle_and_argument_checks_without_a_gpu():

@@ -67,12 +67,11 @@ class Dump:
         return "[" + ",".join(self.struct(d) for d in arr) + "]"
 
     def arg(self, ctype, v):
-        pointer = ctype in (C.c_void_p, C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, (C._Pointer, C.Array)))
         if hasattr(v, "_obj"):                                     # ctypes.byref(descriptor)
             return f"&{self.addr(C.addressof(v._obj))}:{self.struct(v._obj)}"
         if isinstance(v, C.Array):
             return f"{self.addr(C.addressof(v))}:{self.field(type(v), v)}"
-        if pointer:
+        if _lib.sig_codes([ctype]) == "p":
             return self.addr(v)
         return repr(v.value if hasattr(v, "value") else v)
 
